@@ -2,7 +2,16 @@
 """Headline benchmark: crops/sec (encode + codebook-NN), 128x128x3 crops against a
 92232x128 fp32 codebook (BASELINE.json metric), one object per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last timed step's outputs if asked and prints
+the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...).
+Everything else this script measures -- per-kernel timing and roofline, `direct_fp32`, `split_precision`, `config4`, the
+secondary measurements listed below and `cpu_baseline` -- runs only under `--full`.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last timed step returned to its caller, as
+DIR/idx.npy (float64 codebook row indices, [B, 1]; [N * B, 1] gathered over the ranks for N > 1) and DIR/score.npy
+(float32 cosine similarities, same shape).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 Launch forms.  N = 1: this process is the only rank.  N > 1: either start it under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`
@@ -16,13 +25,13 @@ crops per GPU: 4-conv encoder -> dense -> l2-normalise -> codebook scan ->
 arg-max (+ for N > 1 the RCCL all_gather of the (index, score) pairs, the only
 collective on this path).  Rank 0 prints ONE JSON line.
 
-`value` is measured in exact fp32 (fp32 MFMA, bit-equal to an fma chain).  The same
+`value` is measured in exact fp32 (fp32 MFMA, bit-equal to an fma chain).  Under `--full` the same
 line carries a `split_precision` object: the identical step in the opt-in f32x3h
 mode (fp32 in/out, every product as 3 fp16 MFMAs on (hi, lo) operand pairs, fp32
 accumulate; same parity tolerances) -- reported beside
 the headline, never as it.  `--precision f32x3h` makes that mode the measured one.
 
-After the headline (N = 1 only, `--no-extras` skips them) the same line carries the other BASELINE configs and the
+Under `--full`, after the headline (N = 1 only, `--no-extras` skips them) the same line carries the other BASELINE configs and the
 per-detection regime, each measured in this run: `latency` (B = 1, 2, 4 fused encode+nn, eager and as one HIP-graph
 replay), `scan` (the codebook query alone: whole call warm, cold = rotating over 8 codebook copies that exceed the
 256 MB Infinity Cache, fraction of the 8 TB/s HBM peak), `config3` (encode 92232 views: ae_embed), `config5`
@@ -183,28 +192,37 @@ def main():
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=BATCH)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (idx.npy float64, score.npy float32) to DIR")
+    ap.add_argument('--full', action='store_true',
+                    help='also take every measurement beyond the headline (per-kernel timing and roofline, direct_fp32, split_precision, '
+                         'config4, latency, scan, config3, config5, pcie, decoder, cpu_baseline); the --no-* options below trim it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) skip the CPU baseline')
     ap.add_argument('--precision', choices=['f32', 'f32x3h'], default='f32',
                     help='arithmetic of the measured step: f32 (default, exact fp32 MFMA) or f32x3h (split precision)')
-    ap.add_argument('--no-split-precision', action='store_true', help='skip the extra f32x3h measurement')
-    ap.add_argument('--profile-steps', type=int, default=5, help='instrumented per-kernel timing passes after the timed region')
+    ap.add_argument('--no-split-precision', action='store_true', help='(with --full) skip the extra f32x3h and direct_fp32 measurements')
+    ap.add_argument('--profile-steps', type=int, default=5, help='(with --full) instrumented per-kernel timing passes after the timed region')
     ap.add_argument('--force-dist', action='store_true',
-                    help='initialise the RCCL process group and take the multi-GPU code path (pair packing, all_gather, config4) even at world size 1')
-    ap.add_argument('--full-extras', action='store_true', help='(kept for old command lines: config3 at batch 64 is part of the default run since round 6)')
+                    help='initialise the RCCL process group and take the multi-GPU code path (pair packing, all_gather; config4 with --full) even at world size 1')
+    ap.add_argument('--full-extras', action='store_true', help='(kept for old command lines: config3 at batch 64 is part of every --full run since round 6)')
     ap.add_argument('--no-config3-b64', action='store_true',
-                    help='skip config3 at the reference batch size 64 (profiling runs: those launches share the kernel symbols of the headline batch '
+                    help='(with --full) skip config3 at the reference batch size 64 (profiling runs: those launches share the kernel symbols of the headline batch '
                          'and blur the per-symbol averages of rocprofv3 --stats)')
     ap.add_argument('--enc-opt', action='append', default=[], metavar='NAME=INT',
                     help='set an encoder option before measuring (kernel-variant A/B under a profiler); recorded in config')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary measurements (latency, scan, config3, config5, pcie, decoder)')
-    ap.add_argument('--no-config4', action='store_true', help='skip the mixed-batch config4 measurement (eight objects, 256 crops)')
-    ap.add_argument('--config4', action='store_true', help='measure config4 even under --no-extras')
+    ap.add_argument('--no-extras', action='store_true', help='(with --full) skip the secondary measurements (latency, scan, config3, config5, pcie, decoder)')
+    ap.add_argument('--no-config4', action='store_true', help='(with --full) skip the mixed-batch config4 measurement (eight objects, 256 crops)')
+    ap.add_argument('--config4', action='store_true', help='(with --full) measure config4 even under --no-extras')
     ap.add_argument('--dry-run-dist', action='store_true',
                     help='take the N-rank launch path on CPU (gloo): process group + one all_gather, no GPU work (launch-path test)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
+    if args.config4 and not args.full:
+        raise SystemExit('--config4 is a measurement beyond the headline: add --full')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         os.environ['AAE_BENCH_LAUNCHER'] = 'self'
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -259,16 +277,30 @@ def main():
         if use_dist:
             pack_pairs(idx, score, None, packed)                  # one launch: (index, score bits) pairs, the gather payload
             dist.all_gather_into_tensor(gathered, packed)
-        return idx, score
+        return z, idx, score
 
     def fence():
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(precision, winograd=1):
+    def step_outputs(last, x3h_redone):
+        """what the last timed step handed its caller, on the host: (idx float64 [rows, 1], score float32 [rows, 1]); rows = B,
+        or world * B gathered over the ranks"""
+        import numpy as np
+        z, idx, score = last
+        if x3h_redone:                     # settle() recomputed z in exact fp32, in place: the answer derived from it is derived again
+            idx, score = cb.nn(z, 1, 1)
+        if use_dist:                       # (every rank takes part: the gather is collective)
+            pack_pairs(idx, score, None, packed)
+            dist.all_gather_into_tensor(gathered, packed)
+            g = gathered.cpu().numpy()
+            return g[:, :1].astype(np.float64), g[:, 1:].astype(np.int32).view(np.float32)
+        return idx.cpu().numpy().astype(np.float64), score.cpu().numpy().astype(np.float32)
+
+    def measure(precision, winograd=1, keep_outputs=False):
         """W warm-up steps, then exactly K timed steps between barrier+synchronize fences, max over
-        ranks; then per-kernel durations from HIP events on the launch stream."""
+        ranks; under --full then per-kernel durations from HIP events on the launch stream."""
         enc.set_option('precision', 1 if precision == 'f32x3h' else 0)
         enc.set_option('winograd', winograd)
         for kv in args.enc_opt:
@@ -278,7 +310,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
@@ -294,6 +326,15 @@ def main():
         # split precision: the range flags of all forwards of the loop are read here, once, outside the timed region (no
         # host round trip per step); a batch that left the fp16 pair range would have been recomputed in exact fp32
         x3h_redone = enc.settle()
+        res = {
+            'value': round(world * B * args.steps / elapsed, 1),
+            'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+            'rank_ms_per_step': rank_ms,
+            'x3h_batches_recomputed_in_fp32': x3h_redone if precision == 'f32x3h' else None,
+            'outputs': step_outputs(last, x3h_redone) if keep_outputs else None,
+        }
+        if not args.full:
+            return res
         per, order = {}, []
         for _ in range(max(args.profile_steps, 1)):
             _, recs = enc.encode_timed(x)
@@ -326,9 +367,7 @@ def main():
             busy = dict(tj.get('mfma' if precision == 'f32' else 'mfma_x3h', {}).get(traffic_key, {}), source=tj.get('mfma_source'))
         except Exception:
             traffic = None
-        return {
-            'value': round(world * B * args.steps / elapsed, 1),
-            'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+        res.update({
             'roofline': {'bound': 'mfma', 'kernel': dom['kernel'], 'achieved': round(achieved, 2), 'peak': round(peak, 1),
                          'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4), 'traffic': traffic,
                          'traffic_source': ('profiles/traffic.json <- ' + (traffic_src or 'rocprofv3 PMC passes of an earlier run of this command: 2*FETCH_SIZE + WRITE_SIZE') +
@@ -344,15 +383,19 @@ def main():
                          'frac_of_peak_at_delivered_clock': round(achieved / (peak * busy['delivered_GHz'] / 2.4), 4) if busy.get('delivered_GHz') else None},
             'encoder_tflops': round(cfg.flops_per_crop() * B / (sum(k['ms'] for k in kernels) * 1e-3) / 1e12, 2),
             'kernels': kernels,
-            'rank_ms_per_step': rank_ms,
-            'x3h_batches_recomputed_in_fp32': x3h_redone if precision == 'f32x3h' else None,
-        }
+        })
+        return res
 
-    main_res = measure(args.precision)
+    main_res = measure(args.precision, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'idx.npy'), main_res['outputs'][0])
+        np.save(os.path.join(args.dump_outputs, 'score.npy'), main_res['outputs'][1])
     # the same step on the direct fp32 kernels (option winograd = 0: what rounds 1-4 reported as the headline)
-    direct_res = measure('f32', winograd=0) if args.precision == 'f32' and not args.no_split_precision else None
+    direct_res = measure('f32', winograd=0) if args.full and args.precision == 'f32' and not args.no_split_precision else None
     split_res = None
-    if args.precision == 'f32' and not args.no_split_precision:
+    if args.full and args.precision == 'f32' and not args.no_split_precision:
         split_res = measure('f32x3h')
         enc.set_option('precision', 0)
     enc.set_option('winograd', 1)
@@ -381,7 +424,7 @@ def main():
                        CodebookEngine(synth.make_codebook(N_ROWS, 128, seed=7 + i), device=dev))
         return objs[i]
 
-    if not args.no_config4 and (not args.no_extras or args.config4) and args.precision == 'f32':
+    if args.full and not args.no_config4 and (not args.no_extras or args.config4) and args.precision == 'f32':
         # ---- BASELINE config 4 as SURVEY 8d defines it: ONE mixed batch of 256 crops with class labels integers(0, 8): EIGHT objects at
         # every N, object o on rank o mod N (8 / N objects per GPU); every rank runs encode + scan on its buckets (the host routes by
         # class id, as the reference's per-box loop does, m3_interface/ae_pose_estimator.py:143-170) and -- N > 1 -- one RCCL all_gather
@@ -438,7 +481,7 @@ def main():
                              'launches_per_step_besides_encode_nn': 'one pack_pairs per rank, %sunpack_pairs (buffers owned by the cached plan)' % ('all_gather, ' if use_dist else ''),
                              'query': ('aae_encode_nn_multi: one C call for the rank\'s %d buckets, %d grouped launches (one launch per layer across the objects: conv1, the Winograd conv layers, the dense layer, + one for the incomplete four-image blocks of conv4; '
                                        'the codebook scans as one launch per row-part count + one reduce launch)' % (len(order), mq4.launches or 0)) if mq4 is not None else 'aae_encode_nn per object'}
-    if not use_dist and not args.no_extras and args.precision == 'f32':
+    if args.full and not use_dist and not args.no_extras and args.precision == 'f32':
         from augmentedautoencoder_amd.engine import CapturedNearestNeighbour, DecoderEngine, StreamingNearestNeighbour
         from augmentedautoencoder_amd.weights import DecoderConfig
         import numpy as np
@@ -677,15 +720,18 @@ def main():
                                    'cosine-NN vs %dx128 fp32 codebook, top-1' % (B, N_ROWS),
                        'batch_per_gpu': B, 'codebook_rows': N_ROWS, 'latent': 128,
                        'parallelism': 'objects sharded 1 per GPU; all_gather of (idx, score) only' if use_dist else 'single GPU'},
-            'roofline': main_res['roofline'],
-            'encoder_tflops': main_res['encoder_tflops'],
-            'encoder_tflops_note': 'algorithmic (direct-form) flops of the encoder / kernel time: with the polyphase-Winograd conv layers a TF-EQUIVALENT that may exceed the matrix peak',
-            'kernels': main_res['kernels'],
         }
+        if args.full:
+            out.update({
+                'roofline': main_res['roofline'],
+                'encoder_tflops': main_res['encoder_tflops'],
+                'encoder_tflops_note': 'algorithmic (direct-form) flops of the encoder / kernel time: with the polyphase-Winograd conv layers a TF-EQUIVALENT that may exceed the matrix peak',
+                'kernels': main_res['kernels'],
+            })
         if use_dist:
             out['rccl_world_size'] = dist.get_world_size()
             out['launched_by'] = os.environ.get('AAE_BENCH_LAUNCHER', 'external launcher (torch.distributed.run)')
-            if world > 1:
+            if world > 1 and args.full:
                 out['multi_gpu_note'] = ('N > 1: the line carries the weak-scaling headline and config4 only; cpu_baseline, latency, scan, config3, '
                                          'config5, pcie_inclusive and decoder are single-GPU measurements and are reported by the N = 1 run')
             out['rank_ms_per_step'] = {'min': min(main_res['rank_ms_per_step']), 'max': max(main_res['rank_ms_per_step']),
@@ -704,7 +750,7 @@ def main():
                                       'batches_recomputed_in_fp32': split_res['x3h_batches_recomputed_in_fp32'],
                                       'range_check': 'per-forward device flags, read once after the timed loop (no host sync per step)',
                                       'note': 'opt-in mode, same parity tolerances (cosine 1e-5, tie-aware index equality); not the headline'}
-        if not use_dist and not args.no_cpu_baseline:
+        if args.full and not use_dist and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(weights, E, crops)
         print(json.dumps(out))
     if use_dist:

@@ -1,6 +1,6 @@
 """bench.py launch forms: the driver starts `python bench.py --gpus N ...` WITHOUT a launcher;
 for N > 1 the script must become its own launcher (one rank per GPU under torch.distributed.run) or say, in one JSON
-line and without a traceback, why it cannot."""
+line and without a traceback, why it cannot.  A plain run measures the headline alone; the rest needs --full."""
 import json
 import os
 import subprocess
@@ -47,10 +47,48 @@ def test_more_ranks_than_gpus_is_one_json_line_with_an_error_and_no_traceback():
     assert 'Traceback' not in err
 
 
+def test_measurements_beyond_the_headline_ask_for_full():
+    p = subprocess.run([sys.executable, BENCH, '--config4', '--steps', '1', '--warmup', '0'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode != 0 and '--full' in p.stderr.decode() and 'Traceback' not in p.stderr.decode()
+    p = subprocess.run([sys.executable, BENCH, '--steps', '0'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode != 0 and '--steps' in p.stderr.decode() and 'Traceback' not in p.stderr.decode()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps, the headline fields and none of the --full
+    measurements; DIR holds what the last timed step returned, the answers bench.py's seeded inputs give in this process."""
+    import numpy as np
+    import torch
+    from augmentedautoencoder_amd import synth
+    from augmentedautoencoder_amd.engine import CodebookEngine, EncoderEngine
+    from augmentedautoencoder_amd.weights import EncoderConfig
+    rc, out, err = _run(['--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / 'out')])
+    assert rc == 0, err[-3000:]
+    line = out[-1]
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 1000
+    assert line['metric'].startswith('crops/sec') and line['unit'] == 'crops/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert not {'kernels', 'roofline', 'direct_fp32', 'split_precision', 'config4', 'latency', 'scan', 'config5', 'cpu_baseline'} & set(line)
+    idx, score = np.load(tmp_path / 'out' / 'idx.npy'), np.load(tmp_path / 'out' / 'score.npy')
+    assert idx.dtype == np.float64 and score.dtype == np.float32 and idx.shape == score.shape == (256, 1)
+    enc = EncoderEngine(EncoderConfig(), synth.make_weights(seed=2024), max_batch=256)
+    cb = CodebookEngine(synth.make_codebook(92232, 128, seed=7))
+    z = enc.encode(synth.make_crops(256, seed=1234))
+    cs = cb.similarity(z).cpu().numpy()
+    i2, s2 = cb.nn(z, 1, 1)
+    torch.cuda.synchronize()
+    assert np.abs(score - s2.cpu().numpy()).max() <= 1e-6
+    rows = np.arange(256)
+    assert (cs[rows, idx[:, 0].astype(np.int64)] >= cs.max(axis=1) - 1e-6).all()         # the arg-max, up to a near-tie
+    assert (idx[:, 0] == i2.cpu().numpy()[:, 0]).mean() > 0.95
+    enc.close()
+    cb.close()
+
+
 @pytest.mark.gpu
 def test_rccl_code_path_of_the_bench_on_one_gpu():
     """the N > 1 code path (RCCL process group, pair packing, all_gather, config4) as a subprocess at world size 1"""
-    rc, out, err = _run(['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--no-extras', '--config4', '--no-split-precision',
+    rc, out, err = _run(['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--full', '--no-extras', '--config4', '--no-split-precision',
                          '--no-cpu-baseline', '--profile-steps', '1'])
     assert rc == 0, err[-3000:]
     line = out[-1]

@@ -4,7 +4,7 @@
 #   /usr/local/graft/bin/gpurun --timeout N -- 'bash tools/gpu_run.sh <tag> <step> [<step> ...]'      -> gpurun_out/<tag>/
 # Steps (in the order given):
 #   smoke | tests | tests_experiments | bench | bench_quick | bench_config4
-#   bench_rocprof              the default bench command under rocprofv3 --kernel-trace --stats (kernel_stats CSV kept, big traces dropped)
+#   bench_rocprof              the --full bench command under rocprofv3 --kernel-trace --stats (kernel_stats CSV kept, big traces dropped)
 #   pmc_bench                  the six PMC passes (each its own run, --kernel-trace only, as the pool requires) of the headline step + pmc_summary
 #   prof:<name>:<cmd>          rocprofv3 stats + the six PMC passes of an arbitrary command (commas stand for spaces) -> <name>_trace/, <name>_pmc*/
 #   stats:<name>:<cmd>         rocprofv3 --kernel-trace --stats of an arbitrary command + per-symbol durations / gaps (tools/trace_gaps.py)
@@ -43,13 +43,13 @@ for step in "$@"; do
     smoke)        timeout -s KILL 600 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?" >> $OUT/smoke.log; tail -4 $OUT/smoke.log ;;
     tests)        timeout -s KILL 1500 python -m pytest tests -m gpu -x -q --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log; tail -4 $OUT/pytest_gpu.log | tee $OUT/pytest_gpu_tail.log ;;
     tests_experiments) AAE_EXPERIMENTS=1 timeout -s KILL 1500 python -m pytest tests -m gpu -x -q --timeout 900 > $OUT/pytest_gpu_experiments.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu_experiments.log; tail -4 $OUT/pytest_gpu_experiments.log | tee $OUT/pytest_gpu_experiments_tail.log ;;
-    bench)        timeout -s KILL 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cut -c1-700 $OUT/bench_default.json ;;
-    bench_quick)  timeout -s KILL 600 python bench.py --no-extras > $OUT/bench_quick.json 2> $OUT/bench_quick.err; cut -c1-700 $OUT/bench_quick.json ;;
-    bench_config4) timeout -s KILL 600 python bench.py --no-extras --config4 > $OUT/bench_config4.json 2> $OUT/bench_config4.err; python -c "import json; r=json.load(open('$OUT/bench_config4.json')); print(r['value'], r['config4']['value'], r['config4']['ms_per_batch'])" ;;
-    bench_rocprof) ( cd /tmp; timeout -s KILL 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $ROOT/bench.py --no-config3-b64 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err )
+    bench)        timeout -s KILL 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cut -c1-700 $OUT/bench_default.json ;;
+    bench_quick)  timeout -s KILL 600 python bench.py --full --no-extras > $OUT/bench_quick.json 2> $OUT/bench_quick.err; cut -c1-700 $OUT/bench_quick.json ;;
+    bench_config4) timeout -s KILL 600 python bench.py --full --no-extras --config4 > $OUT/bench_config4.json 2> $OUT/bench_config4.err; python -c "import json; r=json.load(open('$OUT/bench_config4.json')); print(r['value'], r['config4']['value'], r['config4']['ms_per_batch'])" ;;
+    bench_rocprof) ( cd /tmp; timeout -s KILL 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $ROOT/bench.py --full --no-config3-b64 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err )
                   find $OUT/trace -name "*kernel_trace.csv" -size +8M -delete
                   cut -c1-170 $(find $OUT/trace -name "*kernel_stats.csv" | head -1) | head -14 ;;
-    pmc_bench)    prof bench python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --profile-steps 1 ;;
+    pmc_bench)    prof bench python $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --profile-steps 1 ;;
     prof:*)       name=$(echo $step | cut -d: -f2); cmd=$(echo $step | cut -d: -f3- | tr ',' ' '); prof $name $cmd ;;
     stats:*)      name=$(echo $step | cut -d: -f2); cmd=$(echo $step | cut -d: -f3- | tr ',' ' ')
                   ( cd /tmp; timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${name}_trace -o $name -- $cmd > $OUT/${name}_trace.log 2>&1 )
