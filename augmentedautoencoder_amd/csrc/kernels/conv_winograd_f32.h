@@ -58,7 +58,7 @@ struct ConvWinoArgs {
 #endif
 };
 #ifdef AAE_WINO_STAMPS
-constexpr int kWinoStampSlots = 48;
+constexpr int kWinoStampSlots = 64;
 #define AAE_WINO_STAMP(a, slot) do { if ((threadIdx.x & 63) == 0) (a).stamps[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * aae::kWinoStampSlots + (slot)] = aae::clock_ticks(); } while (0)
 #else
 #define AAE_WINO_STAMP(a, slot) do {} while (0)
@@ -163,6 +163,45 @@ __device__ __forceinline__ f32x4 wino_add4(f32x4 a, f32x4 b) {
 __device__ __forceinline__ f32x4 wino_sub4(f32x4 a, f32x4 b) {
     const f32x2 lo = wino_pk_sub(a.lo, b.lo), hi = wino_pk_sub(a.hi, b.hi);
     return f32x4{lo.x, lo.y, hi.x, hi.y};
+}
+// single fp32 add / subtract / negated add for the output transform (as asm: left to the vectorizer, the drain's scalar sums become
+// packed adds of neighbouring accumulator registers plus the moves that regroup them into pixel quads -- more instructions and spills)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float wino_add1(float a, float b) {
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float wino_sub1(float a, float b) {
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float wino_nadd1(float a, float b) {      // -a - b
+    float r;
+    asm("v_sub_f32 %0, -%1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#else
+__host__ __device__ inline float wino_add1(float a, float b) { return a + b; }
+__host__ __device__ inline float wino_sub1(float a, float b) { return a - b; }
+__host__ __device__ inline float wino_nadd1(float a, float b) { return -a - b; }
+#endif
+// An MFMA result read by a VALU instruction needs the XDL write -> VALU read wait states first (16-pass v_mfma_f32_32x32x2_f32: 18).  hipcc
+// pads only for readers it can see, and the drain's first readers of the accumulators are the asm adds above.  This statement takes every
+// accumulator tile of a 32-channel half as an operand -- so it stands behind the last MFMA that writes any of them and in front of every
+// reader -- and holds 20 wait states inside its string.
+template <int N>
+__device__ __forceinline__ void wino_acc_fence(f32x16 (&c)[N]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(N == 6 || N == 8, "2 PB accumulator tiles");
+    if constexpr (N == 8)
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]));
+    else
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]));
+#else
+    (void)c;
+#endif
 }
 
 // Block geometry shared by the phases of a launch: which images / window a block covers and where a tile of a wave lies.
@@ -288,7 +327,7 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
     constexpr int NH = WIDE ? 2 : 1;                            // 32-channel halves per wave
     constexpr int kOffA = TA == 2 ? 1 : 0, kOffB = TB == 2 ? 1 : 0;   // a 2-tap dimension starts one sample into the window
     static_assert(CHAIN == 0 || !WIDE, "the chained form passes one wave's weight fragments between the components");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);        // (a scalar: every choice by wave below is a branch, not a select)
     const int mh = wave & 1, nh = WIDE ? 0 : (wave >> 1) & 1, ph = WIDE ? wave >> 1 : wave >> 2, m = lane & 31, h = lane >> 5;
     int li, lty, ltx;
     wino_tile<GEOM>(mh, m, li, lty, ltx);
@@ -365,9 +404,10 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
 #pragma unroll
         for (int s2 = 0; s2 < PB; ++s2) {
             const int ob = fB(s2 + kOffB);
+            // (unit i = 1 follows unit i = 0 of the same group: raw[PB ...] still holds that group's row offA2 -- the transform only reads raw)
             if (i == 0) raw[s2] = plane[offA0 + ob];
             else if (TA == 3) raw[s2] = plane[offA1 + ob];
-            raw[PB + s2] = plane[offA2 + ob];
+            if (i == 0) raw[PB + s2] = plane[offA2 + ob];
         }
     };
     auto step_a = [&](int i, const f32x4 (&raw)[2 * PB], f32x4 (&w)[PB]) {       // rows of B^T d along A
@@ -477,73 +517,91 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
             uout[p] = buffer_load4_s(nrs, nlane + (p % NPB) * 1024u, next_two_rows ? (p / NPB) * NPB * 1024u : (p / NPB) * (NNP * 1024u));
     }
     buf0 = (buf0 + nst) & 1;
+#pragma unroll
+    for (int n2 = 0; n2 < NH; ++n2) wino_acc_fence(acc[n2]);
 
     // ---- output transform.  Along A the rows of A^T m split over the two waves:
     //        ph 0: q0 = m0 + m1, q1 = m1        ph 1, F(2, 3): q0 = m2, q1 = -m2 - m3        ph 1, F(2, 2): q0 = 0, q1 = -m2
     //      each wave applies A along B to its part: four partial outputs (the pixels of a tile) per accumulator register.
-    auto partial = [&](int n2, int r, float (&y)[4]) {
-        float q0[PB], q1[PB];
+    //      ph is wave-uniform: the drain is compiled once per half (PH) and chosen by a scalar branch -- no per-lane selects between the two
+    //      halves' formulas (which cost as many VALU cycles as the formulas themselves).
+    auto drain = [&](auto ph_tag) {
+        constexpr int PH = decltype(ph_tag)::value;
+        auto partial = [&](int n2, int r, float (&y)[4]) {
+            constexpr bool kNoQ0 = PH == 1 && TA == 2;      // (the third row of F(2, 2): q0 = 0, its sums are +0)
+            float q0[PB], q1[PB];
 #pragma unroll
-        for (int j = 0; j < PB; ++j) {
-            const float mA = acc[n2][j][r], mB = acc[n2][PB + j][r];
-            if (ph == 0) { q0[j] = mA + mB; q1[j] = mB; }
-            else if (TA == 3) { q0[j] = mA; q1[j] = -mA - mB; }
-            else { q0[j] = 0.f; q1[j] = -mA; }
-        }
-        // (pixel k = 2 iA + iB is output (dy, dx) = (iA, iB), or (iB, iA) when A = columns: stored as 2 dy + dx)
-        float t[4];
-        if (TB == 3) {
-            t[0] = q0[0] + q0[1] + q0[2];
-            t[1] = q0[1] - q0[2] - q0[3];
-            t[2] = q1[0] + q1[1] + q1[2];
-            t[3] = q1[1] - q1[2] - q1[3];
-        } else {
-            t[0] = q0[0] + q0[1];
-            t[1] = q0[1] - q0[2];
-            t[2] = q1[0] + q1[1];
-            t[3] = q1[1] - q1[2];
-        }
-        y[0] = t[0];
-        y[1] = SWAP ? t[2] : t[1];
-        y[2] = SWAP ? t[1] : t[2];
-        y[3] = t[3];
-    };
-    // Every wave first turns its accumulators into partial outputs, then the two waves of a pair add them into the exchange buffer in two
-    // rounds with all eight waves at work in both: round one takes the registers r with r % 2 == ph, round two the others (the order of the
-    // two additions into an element is fixed: deterministic sums).
-    f32x4 yv[NH][16];
-#pragma unroll
-    for (int n2 = 0; n2 < NH; ++n2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float y[4];
-            partial(n2, r, y);
-            yv[n2][r] = f32x4{y[0], y[1], y[2], y[3]};
-        }
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-#pragma unroll
-        for (int n2 = 0; n2 < NH; ++n2) {
-            f32x4* xq = reinterpret_cast<f32x4*>(xch_all) + (size_t)(mh + 2 * (nh + n2)) * 16 * 64 + lane;
-            if (ACCUMULATE || round == 1) {
-                f32x4 old[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) old[e] = ph == round ? xq[(2 * e) * 64] : xq[(2 * e + 1) * 64];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    if (ph == round) xq[(2 * e) * 64] = old[e] + yv[n2][2 * e];
-                    else xq[(2 * e + 1) * 64] = old[e] + yv[n2][2 * e + 1];
-                }
+            for (int j = 0; j < PB; ++j) {
+                const float mA = acc[n2][j][r], mB = acc[n2][PB + j][r];
+                if (PH == 0) { q0[j] = wino_add1(mA, mB); q1[j] = mB; }
+                else if (TA == 3) { q0[j] = mA; q1[j] = wino_nadd1(mA, mB); }
+                else { q0[j] = 0.f; q1[j] = -mA; }
+            }
+            // (pixel k = 2 iA + iB is output (dy, dx) = (iA, iB), or (iB, iA) when A = columns: stored as 2 dy + dx)
+            float t[4];
+            if (TB == 3) {
+                t[0] = kNoQ0 ? 0.f : wino_add1(wino_add1(q0[0], q0[1]), q0[2]);
+                t[1] = kNoQ0 ? 0.f : wino_sub1(wino_sub1(q0[1], q0[2]), q0[3]);
+                t[2] = wino_add1(wino_add1(q1[0], q1[1]), q1[2]);
+                t[3] = wino_sub1(wino_sub1(q1[1], q1[2]), q1[3]);
             } else {
+                t[0] = kNoQ0 ? 0.f : wino_add1(q0[0], q0[1]);
+                t[1] = kNoQ0 ? 0.f : wino_sub1(q0[1], q0[2]);
+                t[2] = wino_add1(q1[0], q1[1]);
+                t[3] = wino_sub1(q1[1], q1[2]);
+            }
+            y[0] = t[0];
+            y[1] = SWAP ? t[2] : t[1];
+            y[2] = SWAP ? t[1] : t[2];
+            y[3] = t[3];
+        };
+        // Every wave first turns its accumulators into partial outputs, then the two waves of a pair add them into the exchange buffer in two
+        // rounds with all eight waves at work in both: round one takes the registers r with r % 2 == ph, round two the others (the order of the
+        // two additions into an element is fixed: deterministic sums).
+        f32x4 yv[NH][16];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    if (ph == round) xq[(2 * e) * 64] = yv[n2][2 * e];
-                    else xq[(2 * e + 1) * 64] = yv[n2][2 * e + 1];
+        for (int n2 = 0; n2 < NH; ++n2)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float y[4];
+                partial(n2, r, y);
+                yv[n2][r] = f32x4{y[0], y[1], y[2], y[3]};
+            }
+#ifdef AAE_WINO_STAMPS
+        AAE_WINO_STAMP(a, 48 + 4 * kPhaseNo + 0);
+#endif
+#pragma unroll
+        for (int round = 0; round < 2; ++round) {
+            const int par = PH == round ? 0 : 1;         // (the register parity this wave adds in this round)
+#pragma unroll
+            for (int n2 = 0; n2 < NH; ++n2) {
+                f32x4* xq = reinterpret_cast<f32x4*>(xch_all) + (size_t)(mh + 2 * (nh + n2)) * 16 * 64 + lane;
+                if (ACCUMULATE || round == 1) {
+                    f32x4 old[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) old[e] = xq[(2 * e + par) * 64];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xq[(2 * e + par) * 64] = old[e] + yv[n2][2 * e + par];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xq[(2 * e + par) * 64] = yv[n2][2 * e + par];
                 }
             }
+#ifdef AAE_WINO_STAMPS
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            AAE_WINO_STAMP(a, 48 + 4 * kPhaseNo + 1 + 2 * round);
+#endif
+            // The second round's barrier is left to the next component when that one takes a stage barrier before its own drain (a chained
+            // component with at least two stages): the partner's round-two additions are then ordered before this wave's next round one by
+            // that barrier, and nothing else reads the exchange buffer in between.
+            if (round == 0 || !(CHAIN & 2) || nst < 2) __syncthreads();
+#ifdef AAE_WINO_STAMPS
+            if (round == 0) AAE_WINO_STAMP(a, 48 + 4 * kPhaseNo + 2);
+#endif
         }
-        __syncthreads();
-    }
+    };
+    if (ph == 0) drain(std::integral_constant<int, 0>());
+    else drain(std::integral_constant<int, 1>());
     AAE_WINO_STAMP(a, 4 * kPhaseNo + 3);
 }
 

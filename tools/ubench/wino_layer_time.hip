@@ -5,7 +5,9 @@
 //   * every block mapping xcd_cols = 0 (plain), 1, 2, 4, 8 where the layer allows it (conv_winograd_f32.h: wino_block);
 //   * built with -DAAE_WINO_STAMPS: one launch per layer with in-kernel shader-clock stamps per wave at every phase boundary, reduced here
 //     to "cycles per block in: phase prologue (weights + first stage fill + barrier) | K loop | output transform | final store", the K
-//     loop's MFMA-issue efficiency, and the spread over the waves (which XCD a block ran on is recorded too: the mapping's assumption).
+//     loop's MFMA-issue efficiency, and the spread over the waves (which XCD a block ran on is recorded too: the mapping's assumption);
+//     each output transform split into its VALU part (accumulators -> partial pixels), the LDS traffic of the two exchange rounds (stamped
+//     behind an lgkmcnt(0) wait) and the barrier wait behind each (a round whose barrier the next phase takes shows ~0).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I augmentedautoencoder_amd/csrc -o wino_layer_time tools/ubench/wino_layer_time.hip
 //   hipcc ... -DAAE_WINO_STAMPS -o wino_layer_stamps tools/ubench/wino_layer_time.hip
 #include <hip/hip_runtime.h>
@@ -100,6 +102,7 @@ int main(int argc, char** argv) {
             CHECK(hipMemcpy(hs.data(), dst, nstamp * 8, hipMemcpyDeviceToHost));
             // per block: earliest entry / latest exit over its 8 waves; per phase the wave-mean of every segment
             double seg[4][3] = {{0}}, store = 0, span = 0, kstage[7] = {0}, wave_kloop[8] = {0}, units[2][6] = {{0}}, units_w[2][8][6] = {{{0}}};
+            double drain[4][5] = {{0}};         // per phase: accumulators -> partial pixels (VALU) | round 1 LDS | round 1 barrier | round 2 LDS | round 2 barrier
             long long nb = 0;
             int xcd_ok = 0, xcd_seen = 0;
             for (unsigned b = 0; b < grid; ++b) {
@@ -116,6 +119,11 @@ int main(int argc, char** argv) {
                         seg[ph][1] += (double)(st[4 * ph + 2] - st[4 * ph + 1]) / 8;
                         seg[ph][2] += (double)(st[4 * ph + 3] - st[4 * ph + 2]) / 8;
                         wave_kloop[w] += (double)(st[4 * ph + 2] - st[4 * ph + 1]);
+                        const long long* d = st + 48 + 4 * ph;
+                        if (d[0] && d[1] && d[2] && d[3]) {
+                            const long long edge[6] = {st[4 * ph + 2], d[0], d[1], d[2], d[3], st[4 * ph + 3]};
+                            for (int k = 0; k < 5; ++k) drain[ph][k] += (double)(edge[k + 1] - edge[k]) / 8;
+                        }
                     }
                     store += (double)(st[16] - st[15]) / 8;
                     for (int k = 0; k < 7; ++k)
@@ -143,6 +151,11 @@ int main(int argc, char** argv) {
                        seg[ph][1] * inv, ideal, ideal / (seg[ph][1] * inv), seg[ph][2] * inv);
                 psum += seg[ph][0] * inv; ksum += seg[ph][1] * inv; osum += seg[ph][2] * inv; ideal_sum += ideal;
             }
+            printf(", \"output_transform_split\": [");
+            for (int ph = 0; ph < 4; ++ph)
+                printf("%s{\"valu\": %.0f, \"lds_round1\": %.0f, \"barrier_round1\": %.0f, \"lds_round2\": %.0f, \"barrier_round2\": %.0f}", ph ? ", " : "",
+                       drain[ph][0] * inv, drain[ph][1] * inv, drain[ph][2] * inv, drain[ph][3] * inv, drain[ph][4] * inv);
+            printf("]");
             printf(", \"final_store\": %.0f, \"sum\": {\"prologues\": %.0f, \"k_loops\": %.0f, \"mfma_cycles\": %.0f, \"output_transforms\": %.0f}", store * inv, psum, ksum, ideal_sum, osum);
             printf(", \"phase0_stage_cycles\": [");
             for (int k = 0; k < 7; ++k) printf("%s%.0f", k ? ", " : "", kstage[k] * inv);

@@ -21,3 +21,6 @@ for path in sys.argv[1:]:
         print('%s | span %d: prologues %d kloops %d (mfma %d, eff %.3f) out-transforms %d store %d | stage cycles %s | waves0-3 units %s wait %d | waves4-7 units %s wait %d' % (
             head, c['span'], s['prologues'], s['k_loops'], s['mfma_cycles'], s['mfma_cycles'] / s['k_loops'], s['output_transforms'], c['final_store'],
             c['phase0_stage_cycles'][:4], [int(x) for x in old[:4]], old[4], [int(x) for x in yng[:4]], yng[4]))
+        for ph, d in enumerate(c.get('output_transform_split', [])):
+            print('    phase %d output transform: valu %d | lds %d + %d | barrier %d + %d' % (ph, d['valu'], d['lds_round1'], d['lds_round2'],
+                                                                                              d['barrier_round1'], d['barrier_round2']))
