@@ -303,6 +303,8 @@ int aae_encoder_set_option(aae_encoder* enc, const char* name, int value) {
         enc->winograd = value;
     } else if (!strcmp(name, "winograd_wide")) {
         enc->winograd_wide = value ? 1 : 0;
+    } else if (!strcmp(name, "winograd_stage32")) {
+        enc->winograd_stage32 = value ? 1 : 0;
     } else if (!strcmp(name, "winograd_min_batch")) {
         enc->winograd_min_batch = value < 1 ? 1 : value;
     } else if (!strcmp(name, "winograd_min_fill_pct")) {

@@ -590,7 +590,7 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
     aae::ConvWinoLayerArgs p;
     p.c = a;
     for (int i = 0; i < 4; ++i) p.U4[i] = L.wino[i];
-    wino_layer_launch(L.wino_geom, enc->winograd_wide, grid, stream, p);
+    wino_layer_launch(L.wino_geom, enc->winograd_wide, enc->winograd_stage32, grid, stream, p);
     // (the record carries the flops the kernel EXECUTES -- 49 products per 2 x 2 outputs and channel pair where the direct form
     //  multiplies 100 -- so that its TFLOP/s figure is a statement about the kernel)
     snprintf(label, sizeof(label), "%s:conv_wino_f32 layer (25 taps as 49 products per 2x2 outputs) M=%d N=%d C=%d", name, B * L.Ho * L.Wo, L.Cout, L.Cin);

@@ -6,8 +6,9 @@
 namespace aae_host {
 
 #ifdef AAE_WINO_DECLARATIONS_ONLY
-void wino_layer_launch(int geom, int wide, unsigned grid, hipStream_t stream, const aae::ConvWinoLayerArgs& p);
-void wino_layer_multi_launch(int geom, unsigned grid, hipStream_t stream, const aae::ConvWinoMultiArgs& p);
+// (stage32: 32-channel stages where the layer allows them -- aae::wino_layer_stage_channels; the same bits either way)
+void wino_layer_launch(int geom, int wide, int stage32, unsigned grid, hipStream_t stream, const aae::ConvWinoLayerArgs& p);
+void wino_layer_multi_launch(int geom, int stage32, unsigned grid, hipStream_t stream, const aae::ConvWinoMultiArgs& p);
 void wino_set_attributes();
 #else
 #ifdef AAE_WINO_TU
@@ -15,7 +16,7 @@ void wino_set_attributes();
 #else
 #define AAE_WINO_LINKAGE static
 #endif
-AAE_WINO_LINKAGE void wino_layer_launch(int geom, int wide, unsigned grid, hipStream_t stream, const aae::ConvWinoLayerArgs& p) {
+AAE_WINO_LINKAGE void wino_layer_launch(int geom, int wide, int stage32, unsigned grid, hipStream_t stream, const aae::ConvWinoLayerArgs& p) {
 #ifdef AAE_EXPERIMENTS
     if (wide) {      // blocks of 4 waves over both 32-channel halves: measured 13 % slower than two waves per SIMD (tools/ubench/wino_layer_time.hip)
         if (geom == 0) AAE_LAUNCH((aae::conv_wino_layer_kernel<0, true>), dim3(grid), dim3(256), aae::wino_layer_smem_bytes<0>(), stream, p);
@@ -24,14 +25,20 @@ AAE_WINO_LINKAGE void wino_layer_launch(int geom, int wide, unsigned grid, hipSt
     }
 #endif
     (void)wide;
-    if (geom == 0) AAE_LAUNCH((aae::conv_wino_layer_kernel<0, false>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<0>(), stream, p);
+    if (aae::wino_layer_stage_channels(geom, p.c.Cin, stage32 != 0) == 32)
+        AAE_LAUNCH((aae::conv_wino_layer_kernel<0, false, 32>), dim3(grid), dim3(512), (aae::wino_layer_smem_bytes<0, 32>()), stream, p);
+    else if (geom == 0) AAE_LAUNCH((aae::conv_wino_layer_kernel<0, false>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<0>(), stream, p);
     else AAE_LAUNCH((aae::conv_wino_layer_kernel<1, false>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<1>(), stream, p);
 }
-AAE_WINO_LINKAGE void wino_layer_multi_launch(int geom, unsigned grid, hipStream_t stream, const aae::ConvWinoMultiArgs& p) {
-    if (geom == 0) AAE_LAUNCH((aae::conv_wino_layer_multi_kernel<0>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<0>(), stream, p);
+AAE_WINO_LINKAGE void wino_layer_multi_launch(int geom, int stage32, unsigned grid, hipStream_t stream, const aae::ConvWinoMultiArgs& p) {
+    if (aae::wino_layer_stage_channels(geom, p.c.Cin, stage32 != 0) == 32)
+        AAE_LAUNCH((aae::conv_wino_layer_multi_kernel<0, 32>), dim3(grid), dim3(512), (aae::wino_layer_smem_bytes<0, 32>()), stream, p);
+    else if (geom == 0) AAE_LAUNCH((aae::conv_wino_layer_multi_kernel<0>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<0>(), stream, p);
     else AAE_LAUNCH((aae::conv_wino_layer_multi_kernel<1>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<1>(), stream, p);
 }
 AAE_WINO_LINKAGE void wino_set_attributes() {
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_layer_multi_kernel<0, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0, 32>());
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<0, false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0, 32>());
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_layer_multi_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0>());
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_layer_multi_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<1>());
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0>());

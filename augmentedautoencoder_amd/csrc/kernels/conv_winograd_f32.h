@@ -24,7 +24,7 @@
 //           = at most 128 registers, two waves share a SIMD and one's cluster (patch reads, transform, loads) runs under the other's
 //           MFMA burst.  The two halves of the output transform meet through LDS once per phase.  A = rows, or columns when SWAP (the
 //           2 x 3-tap phase: the 3-tap dimension is the one that splits evenly).
-//   K loop = stages of 16 input channels (32 in the one-launch-per-phase form): the block's window of the sub-image (tiles + halo, zero outside the image = the 'SAME'
+//   K loop = stages of 32 input channels (16 for GEOM 1 in the one-launch-per-layer kernel, whose exchange buffer leaves no room for more): the block's window of the sub-image (tiles + halo, zero outside the image = the 'SAME'
 //           padding) goes global -> registers -> LDS, double buffered, laid out [channel quad][image][column parity][row][column / 2]
 //           with pitches that make the patch reads (ds_read_b128 by 32 tiles) conflict-free.  The loop runs in units of one point row,
 //           each ONE cluster + ONE burst (wino_phase_body: the price list of what an instruction costs next to fp32 MFMAs): a lane transforms
@@ -79,9 +79,14 @@ template <int GEOM>
 struct WinoGeom;
 template <>
 struct WinoGeom<0> {         // one image, 8 x 8 tiles: window 18 x 18
-    // (parity pitch 220 instead of 18 * 12 = 216 quads: the fill writes the two column parities of neighbouring pixels from neighbouring
-    //  lanes -- 880 dwords apart they fall into different halves of the 32 banks a ds_write_b128 group uses)
-    static constexpr int kImages = 1, kRows = 18, kCols = 18, kRowPitch = 12, kParityPitch = 220, kImagePitch = 2 * 220;
+    // Row pitch 10 (9 units of samples + 1 spare), parity pitch 18 * 10 = 180, plane 361: small enough for 32-channel stages next to the
+    // layer kernel's exchange buffer (2 x 8 x 361 x 16 B + 64 KB = 154.25 KB of 160), and free of bank conflicts both ways:
+    //   patch reads (ds_read_b128: four groups of 16 lanes, a group conflict-free when its 16-byte units differ mod 16): a tile's unit is
+    //     20 ty + tx + const = 4 ty + tx (mod 16), and wino_tile<0> gives every lane group the 4 x 4 tiles (ty, tx) of one half of the columns;
+    //   fill stores (ds_write_b128: groups of 8 consecutive lanes, conflict-free when their units differ mod 8): the lanes of a group are the
+    //     8 channel quads of a pixel (planes 361 = 1 (mod 8) apart), or the 4 quads of two neighbouring pixels, which differ in their column
+    //     parity (180 = 4 (mod 8) apart).
+    static constexpr int kImages = 1, kRows = 18, kCols = 18, kRowPitch = 10, kParityPitch = 180, kImagePitch = 2 * 180;
 };
 template <>
 struct WinoGeom<1> {         // four images, 4 x 4 tiles each: windows 10 x 10
@@ -94,7 +99,8 @@ constexpr int wino_stage_units() { return 8 * wino_plane_units<GEOM>(); }
 template <int GEOM>
 constexpr int wino_smem_bytes() { return 2 * wino_stage_units<GEOM>() * 16; }
 
-// arguments of the one-launch-per-layer kernel (below) and its LDS budget: 16-channel stages + a 64 KB exchange buffer of its own
+// arguments of the one-launch-per-layer kernel (below) and its LDS budget: stages of STAGE_CH channels + a 64 KB exchange buffer of its own
+// (32-channel stages where they fit -- GEOM 0 -- and the layer has whole ones; 16 otherwise: wino_layer_stage_channels)
 struct ConvWinoLayerArgs {
     ConvWinoArgs c;          // (U, eh, ew, mode unused)
     const float* U4[4];      // index 2 eh + ew
@@ -116,10 +122,13 @@ struct ConvWinoMultiArgs {
     MultiRange range;
     ConvWinoObject obj[kMultiMax];
 };
-template <int GEOM>
-constexpr int wino_layer_stage_bytes() { return 2 * 4 * wino_plane_units<GEOM>() * 16; }
-template <int GEOM>
-constexpr int wino_layer_smem_bytes() { return wino_layer_stage_bytes<GEOM>() + 4 * 64 * 64 * 4; }
+template <int GEOM, int STAGE_CH = 16>
+constexpr int wino_layer_stage_bytes() { return 2 * (STAGE_CH / 4) * wino_plane_units<GEOM>() * 16; }
+template <int GEOM, int STAGE_CH = 16>
+constexpr int wino_layer_smem_bytes() { return wino_layer_stage_bytes<GEOM, STAGE_CH>() + 4 * 64 * 64 * 4; }
+static_assert(wino_layer_smem_bytes<0, 32>() <= 160 * 1024 && wino_layer_smem_bytes<1, 16>() <= 160 * 1024, "LDS of a compute unit");
+// (four 10 x 10 windows are 401 units densely packed: 32-channel stages of GEOM 1 would need 164 KB)
+inline int wino_layer_stage_channels(int geom, int Cin, bool stage32) { return stage32 && geom == 0 && Cin % 32 == 0 ? 32 : 16; }
 
 
 #ifndef AAE_WINO_DECLARATIONS_ONLY      // (the product library compiles the kernels below in a translation unit of their own: aae_wino.hip)
@@ -190,15 +199,18 @@ __host__ __device__ inline float wino_nadd1(float a, float b) { return -a - b; }
 // An MFMA result read by a VALU instruction needs the XDL write -> VALU read wait states first (16-pass v_mfma_f32_32x32x2_f32: 18).  hipcc
 // pads only for readers it can see, and the drain's first readers of the accumulators are the asm adds above.  This statement takes every
 // accumulator tile of a 32-channel half as an operand -- so it stands behind the last MFMA that writes any of them and in front of every
-// reader -- and holds 20 wait states inside its string.
-template <int N>
-__device__ __forceinline__ void wino_acc_fence(f32x16 (&c)[N]) {
+// reader -- and holds 20 wait states inside its string.  (N = 3: the wave with ONE point row of F(2, 2) x F(2, 2) -- it never writes, and
+// its drain never reads, the second row's tiles.)
+template <int N, int M>
+__device__ __forceinline__ void wino_acc_fence(f32x16 (&c)[M]) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    static_assert(N == 6 || N == 8, "2 PB accumulator tiles");
+    static_assert((N == 3 || N == 6 || N == 8) && N <= M, "PB or 2 PB accumulator tiles");
     if constexpr (N == 8)
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]));
-    else
+    else if constexpr (N == 6)
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]));
+    else
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]));
 #else
     (void)c;
 #endif
@@ -257,7 +269,9 @@ __device__ __forceinline__ WinoBlock wino_block(int block, int nbn, int blocks_x
 // tile t (0 ... 31) of the wave with tile half mh: (image of the block, tile row, tile column)
 template <int GEOM>
 __device__ __forceinline__ void wino_tile(int mh, int t, int& ti, int& ty, int& tx) {
-    if (GEOM == 0) { ti = 0; ty = 4 * mh + (t >> 3); tx = t & 7; }
+    // GEOM 0: the lane groups of a ds_read_b128 are the 4-lane chunks c = t >> 2 in {0, 3, 5, 6} | {1, 2, 4, 7} (even | odd number of set
+    // bits): a group takes tile rows c >> 1 = 0 ... 3 of one half of the tile columns (WinoGeom<0>).
+    if (GEOM == 0) { const int c = t >> 2; ti = 0; ty = 4 * mh + (c >> 1); tx = 4 * ((c ^ (c >> 1) ^ (c >> 2)) & 1) + (t & 3); }
     else { ti = 2 * mh + (t >> 4); ty = (t >> 2) & 3; tx = t & 3; }
 }
 
@@ -279,6 +293,13 @@ struct WinoFillPlan {
     static constexpr int kPer = ((kStageQuads + NT - 1) / NT + kParts - 1) / kParts;       // float4 per thread and part
     uint32_t goff[kParts * kPer];
     int lslot[kParts * kPer];
+    // Slot i of thread t is float4 t + NT i of the stage: whole waves have it, one wave at most has it in part of its lanes (those beyond the
+    // stage store zeros to spare units of the stage buffer: no lane of a storing wave is masked off), the waves behind have none.
+    __host__ __device__ static constexpr bool wave_stores(int wave, int i) { return wave * 64 + NT * i < kStageQuads; }
+    // the spare unit of lane number `d` beyond the stage: column kCols / 2 of window row d / kQuads, which lies inside the row pitch and
+    // which no pixel is stored to and no patch read touches (a different unit per lane)
+    static constexpr int kSpareColumn = (WinoGeom<GEOM>::kCols + 1) / 2;
+    static_assert(kSpareColumn < WinoGeom<GEOM>::kRowPitch && 64 / kQuads <= 2 * WinoGeom<GEOM>::kRows && NT % kQuads == 0, "spare units of the stage buffer");
 };
 constexpr uint32_t kWinoOutside = 0x80000000u;      // a lane offset beyond every buffer view: the load returns zeros ('SAME' padding, empty image slots)
 template <int GEOM, int STAGE_CH, int NT>
@@ -287,21 +308,59 @@ __device__ __forceinline__ void wino_fill_plan(const ConvWinoArgs& a, const Wino
     using F = WinoFillPlan<GEOM, STAGE_CH, NT>;
     constexpr int kPlane = wino_plane_units<GEOM>();
     const int cq_per_pixel = a.Cin / 4;
+    // slot 0 by division, the others by walking on: NT / kQuads pixels = (kStepI images, kStepY rows, kStepX columns) further, with carries
+    constexpr int kStep = NT / F::kQuads, kWindow = G::kRows * G::kCols;
+    constexpr int kStepI = kStep / kWindow, kStepY = kStep % kWindow / G::kCols, kStepX = kStep % G::kCols;
+    const int pixel0 = (int)threadIdx.x / F::kQuads, cq = (int)threadIdx.x % F::kQuads;
+    int wi = pixel0 / kWindow, wy = pixel0 % kWindow / G::kCols, wx = pixel0 % G::kCols;
 #pragma unroll
     for (int i = 0; i < F::kParts * F::kPer; ++i) {
         const int idx = (int)threadIdx.x + NT * i;
         f.goff[i] = kWinoOutside;
-        f.lslot[i] = -1;
         if (idx < F::kStageQuads) {
-            const int pixel = idx / F::kQuads, cq = idx - pixel * F::kQuads;
-            const int wi = pixel / (G::kRows * G::kCols), rem = pixel - wi * (G::kRows * G::kCols);
-            const int wy = rem / G::kCols, wx = rem - wy * G::kCols;
             const int uu = wb.wy0 + wy, vv = wb.wx0 + wx, b = wb.img0 + wi;
             if (uu >= 0 && uu < a.Ho && vv >= 0 && vv < a.Wo && b < a.B)
                 f.goff[i] = (uint32_t)(((((size_t)b * a.H + 2 * uu) * a.W + 2 * vv) * cq_per_pixel + cq) * 16);
             f.lslot[i] = cq * kPlane + wi * G::kImagePitch + (wx & 1) * G::kParityPitch + wy * G::kRowPitch + (wx >> 1);
+        } else {
+            const int d = (idx - F::kStageQuads) & 63, row = d / F::kQuads;       // (only the lanes of the one partly filled wave ever store there)
+            f.lslot[i] = cq * kPlane + (row / G::kRows) * G::kParityPitch + (row % G::kRows) * G::kRowPitch + F::kSpareColumn;
         }
+        wx += kStepX;
+        wy += kStepY + (wx >= G::kCols ? 1 : 0);
+        wx -= wx >= G::kCols ? G::kCols : 0;
+        wi += kStepI + (wy >= G::kRows ? 1 : 0);
+        wy -= wy >= G::kRows ? G::kRows : 0;
     }
+}
+
+// The weight fragments of a component's units 0 and 1 for this wave (8 waves (mh, nh, ph)): rows 0, 1 of 8-channel group 0 -- or, for the
+// wave with ONE point row, that row of groups 0 and 1.  TA x TB: the component's taps.
+template <int TA, int TB>
+__device__ __forceinline__ void wino_first_fragments(const ConvWinoArgs& a, const float* U, const WinoBlock& wb, f32x4 (&u)[8]) {
+    constexpr int PB = TB + 1, NP = (TA + 1) * PB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
+    const int nh = (wave >> 1) & 1, ph = wave >> 2, m = lane & 31, h = lane >> 5, n32 = wb.nb * 2 + nh, KG = a.Cin / 8;
+    const buffer_rsrc urs = make_buffer(U, (uint32_t)((size_t)NP * a.Cin * a.Cout * 4));
+    const uint32_t ulane = (uint32_t)(((size_t)n32 * KG * NP + (size_t)ph * 2 * PB) * 64 + h * 32 + m) * 16u;
+    const bool two_rows = TA == 3 || ph == 0;
+#pragma unroll
+    for (int p = 0; p < 2 * PB; ++p) u[p] = buffer_load4_s(urs, ulane + (p % PB) * 1024u, two_rows ? (p / PB) * PB * 1024u : (p / PB) * (NP * 1024u));
+}
+// The first stage of a block's first component (parities eh, ew) into stage buffer 0; ends behind a block barrier.
+template <int GEOM, int STAGE_CH, int NT>
+__device__ __forceinline__ void wino_first_stage(const ConvWinoArgs& a, int eh, int ew, const WinoFillPlan<GEOM, STAGE_CH, NT>& fill, f32x4* lds) {
+    using F = WinoFillPlan<GEOM, STAGE_CH, NT>;
+    const int wave = wave_uniform((int)threadIdx.x >> 6);
+    const buffer_rsrc xrs = make_buffer(a.x, (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 4));
+    const uint32_t parity_off = (uint32_t)(((size_t)eh * a.W + ew) * a.Cin * 4);
+    f32x4 stg[F::kParts * F::kPer];
+#pragma unroll
+    for (int i = 0; i < F::kParts * F::kPer; ++i) stg[i] = buffer_load4_s(xrs, fill.goff[i], parity_off);
+#pragma unroll
+    for (int i = 0; i < F::kParts * F::kPer; ++i)
+        if (F::wave_stores(wave, i)) lds[fill.lslot[i]] = stg[i];
+    __syncthreads();
 }
 
 // One polyphase component for one block: the K loop over all input channels and the two-wave output transform.  Leaves the block's
@@ -345,13 +404,10 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
     const uint32_t parity_off = (uint32_t)(((size_t)eh * a.W + ew) * a.Cin * 4);          // this component's samples inside the (0, 0) component's offsets
     const uint32_t next_parity_off = (uint32_t)(((size_t)neh * a.W + new_) * a.Cin * 4);
 
+    // (not zeroed: the first MFMA into a tile -- units 0 and 1 of the first stage, or unit 0 of the wave with one point row -- takes the
+    //  constant 0 as its C operand: the same bits as a product added to a zeroed register, without 16 moves per tile behind every
+    //  component boundary -- 511 instructions less per kernel; in time the moves were within the noise)
     f32x16 acc[NH][2 * PB];
-#pragma unroll
-    for (int n2 = 0; n2 < NH; ++n2)
-#pragma unroll
-        for (int p = 0; p < 2 * PB; ++p)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[n2][p][r] = 0.f;
 
     // ---- stage fill: global -> registers -> LDS (the buffer of the next stage is free for the whole of the current one)
     f32x4 stg[kPer];
@@ -359,10 +415,12 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
 #pragma unroll
         for (int i = 0; i < kPer; ++i) stg[i] = buffer_load4_s(xrs, fill.goff[part * kPer + i], soff);
     };
+    // (straight-line stores behind one wait: every lane of a wave that has a slot at all has one to write to -- wino_fill_plan -- and which
+    //  waves have one is a compile-time bound on the scalar wave number)
     auto stage_store = [&](int buf, int part) {
 #pragma unroll
         for (int i = 0; i < kPer; ++i)
-            if (fill.lslot[part * kPer + i] >= 0) lds[buf * kStage + fill.lslot[part * kPer + i]] = stg[i];
+            if (F::wave_stores(wave, part * kPer + i)) lds[buf * kStage + fill.lslot[part * kPer + i]] = stg[i];
     };
     // ---- patch addressing.  A sample at window position (wy, wx) = (2 ty + pA, 2 tx + pB) (or with A and B exchanged when SWAP) lies at
     //      lane_base + fA(pA) + fB(pB).  The A positions this wave reads, in the order (y0, y1, y2) that makes both halves the same
@@ -443,11 +501,18 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
     auto run = [&](auto rows_tag) {
         constexpr int ROWS = decltype(rows_tag)::value, NU = kGroups * ROWS, kPartUnits = NU / kParts;
         static_assert(NU % 2 == 0 && NU % kParts == 0, "units per stage");
-        constexpr int kStoreBack = (kParts == 1 && NU >= 4) ? 2 : 1;            // the fill is stored this many units before its part ends
-        const bool early = ph == 1 && NU >= 4 && kParts == 1;                   // this wave takes the stage barrier in the cluster of unit NU - 2
+        // The fill's part p is loaded in the cluster of unit p kPartUnits and stored kStoreBack units before the part ends: two when a part
+        // has four units (16-channel stages: NU = 4, one part; 32-channel stages: NU = 8, two parts -- the loads have two units to land either
+        // way), one for the wave with one point row (two units per part).  `early`: this wave takes the stage barrier in the cluster of
+        // unit NU - 2, which needs its last store there.
+        constexpr int kStoreBack = kPartUnits >= 4 ? 2 : 1;
+        const bool early = ph == 1 && kStoreBack == 2;
         f32x4 raw[2 * PB], v[PB];
         read_unit(lds + buf0 * kStage + h * kPlane + lane_base, 0, raw);
-        for (int st = 0; st < nst; ++st) {
+        // one stage.  FIRST (a compile-time tag: the component's first stage is peeled off the loop): the units that write an accumulator
+        // tile for the first time start from the constant 0.
+        auto stage_body = [&](int st, auto first_tag) {
+            constexpr bool FIRST = decltype(first_tag)::value;
             const int buf = (buf0 + st) & 1;
             const bool more = st + 1 < nst;
             const bool filling = more || (CHAIN & 2);                            // a stage (this component's next, or the next component's first) is on its way into buf ^ 1
@@ -466,7 +531,7 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
                 // ---- cluster
                 step_a(i, raw, v);
                 step_b(v);
-                if ((st > 0 || t > 0) && (more || t + 1 < NU)) {
+                if ((!FIRST || t > 0) && (more || t + 1 < NU)) {
                     // unit T + 1 = st * NU + t + 1: (group, row) = (T' / ROWS, T' % ROWS); its slot is the one unit T - 1 just released
                     const int tn = (t + 1) % NU, gn = (st + (t + 1) / NU) * kGroups + tn / ROWS;
                     const uint32_t un = (uint32_t)gn * (NP * 1024u) + (tn % ROWS) * PB * 1024u;      // (wave-uniform: a scalar register)
@@ -496,29 +561,35 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
 #pragma unroll
                     for (int j = 0; j < PB; ++j)
 #pragma unroll
-                        for (int n2 = 0; n2 < NH; ++n2)
-                            acc[n2][(ROWS == 2 ? i * PB : 0) + j] = mfma_32x32x2(v[j][q], u[n2][slot * PB + j][q], acc[n2][(ROWS == 2 ? i * PB : 0) + j]);
+                        for (int n2 = 0; n2 < NH; ++n2) {
+                            f32x16& c = acc[n2][(ROWS == 2 ? i * PB : 0) + j];
+                            if (FIRST && t < ROWS && q == 0) c = mfma_32x32x2(v[j][q], u[n2][slot * PB + j][q], f32x16{});
+                            else c = mfma_32x32x2(v[j][q], u[n2][slot * PB + j][q], c);
+                        }
                 sched_fence();
             }
-        }
+        };
+        stage_body(0, std::true_type());
+        for (int st = 1; st < nst; ++st) stage_body(st, std::false_type());
     };
     if (TA == 3 || ph == 0) run(std::integral_constant<int, 2>());
     else run(std::integral_constant<int, 1>());
-    if (STAGE_CH == 32 && !(CHAIN & 2)) __syncthreads();      // (the one-launch-per-phase form: the exchange buffer overlays the stage buffers -- every wave must be through its last patch reads)
+    if (STAGE_CH == 32 && CHAIN == 0) __syncthreads();      // (the one-launch-per-phase form: the exchange buffer overlays the stage buffers -- every wave must be through its last patch reads)
     AAE_WINO_STAMP(a, 4 * kPhaseNo + 2);
     if (CHAIN & 2) {
         // the next component's first weight fragments fly while the accumulators drain and leave
-        constexpr int NPB = NTB + 1, NNP = (NTA + 1) * NPB;
-        const buffer_rsrc nrs = make_buffer(Un, (uint32_t)((size_t)NNP * a.Cin * a.Cout * 4));
-        const uint32_t nlane = (uint32_t)(((size_t)n32 * KG * NNP + (size_t)ph * 2 * NPB) * 64 + h * 32 + m) * 16u;
-        const bool next_two_rows = NTA == 3 || ph == 0;
-#pragma unroll
-        for (int p = 0; p < 2 * NPB; ++p)
-            uout[p] = buffer_load4_s(nrs, nlane + (p % NPB) * 1024u, next_two_rows ? (p / NPB) * NPB * 1024u : (p / NPB) * (NNP * 1024u));
+        wino_first_fragments<NTA, NTB>(a, Un, wb, uout);
     }
     buf0 = (buf0 + nst) & 1;
 #pragma unroll
-    for (int n2 = 0; n2 < NH; ++n2) wino_acc_fence(acc[n2]);
+    for (int n2 = 0; n2 < NH; ++n2) {
+        if constexpr (TA == 2) {
+            if (ph == 1) wino_acc_fence<PB>(acc[n2]);
+            else wino_acc_fence<2 * PB>(acc[n2]);
+        } else {
+            wino_acc_fence<2 * PB>(acc[n2]);
+        }
+    }
 
     // ---- output transform.  Along A the rows of A^T m split over the two waves:
     //        ph 0: q0 = m0 + m1, q1 = m1        ph 1, F(2, 3): q0 = m2, q1 = -m2 - m3        ph 1, F(2, 2): q0 = 0, q1 = -m2
@@ -532,7 +603,7 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
             float q0[PB], q1[PB];
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
-                const float mA = acc[n2][j][r], mB = acc[n2][PB + j][r];
+                const float mA = acc[n2][j][r], mB = kNoQ0 ? 0.f : acc[n2][PB + j][r];
                 if (PH == 0) { q0[j] = wino_add1(mA, mB); q1[j] = mB; }
                 else if (TA == 3) { q0[j] = mA; q1[j] = wino_nadd1(mA, mB); }
                 else { q0[j] = 0.f; q1[j] = -mA; }
@@ -677,40 +748,45 @@ __global__ __launch_bounds__(512) void conv_wino_phase_kernel(ConvWinoArgs a) {
 #endif
 
 // ---- one launch per LAYER: the four phases one behind the other in the block (3 x 3, 3 x 2, 2 x 3, 2 x 2 taps), their outputs added
-//      up in an exchange buffer of its own (64 KB behind the stage buffers, which shrink to 16-channel stages to make room); the
+//      up in an exchange buffer of its own (64 KB behind the stage buffers: stages of STAGE_CH = 32 channels for GEOM 0, 16 for GEOM 1 -- wino_layer_stage_channels); the
 //      output is written once, with bias / ReLU / BN.  No read-modify-write of the output tensor, one prologue / epilogue per four phases.
 //      The phases are CHAINED: each fetches the next one's first stage and first weight fragments while its own K loop ends, so that only
 //      the first phase of a block waits for global memory with an empty matrix pipe.
-template <int GEOM, bool WIDE>
+template <int GEOM, bool WIDE, int STAGE_CH>
 __device__ __forceinline__ void wino_layer_block(const ConvWinoArgs& a, const float* const (&U4)[4], const WinoBlock& wb, unsigned char* smem_raw) {
+    constexpr int SC = STAGE_CH;
+    static_assert(SC == 16 || (SC == 32 && !WIDE), "stage size");
     f32x4* lds = reinterpret_cast<f32x4*>(smem_raw);
-    float* xch = reinterpret_cast<float*>(smem_raw + wino_layer_stage_bytes<GEOM>());
-    WinoFillPlan<GEOM, 16, WIDE ? 256 : 512> fill;
-    wino_fill_plan(a, wb, fill);
+    float* xch = reinterpret_cast<float*>(smem_raw + wino_layer_stage_bytes<GEOM, SC>());
+    WinoFillPlan<GEOM, SC, WIDE ? 256 : 512> fill;
     int buf0 = 0;
     f32x4 ua[8], ub[8];
+    // (the first weight fragments are on their way while the fill plan is built: they depend on nothing but the block's column block)
+    if (!WIDE) wino_first_fragments<3, 3>(a, U4[3], wb, ua);
+    wino_fill_plan(a, wb, fill);
     if (WIDE) {
-        wino_phase_body<3, 3, false, GEOM, 16, false, WIDE>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
-        wino_phase_body<3, 2, false, GEOM, 16, true, WIDE>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
-        wino_phase_body<3, 2, true, GEOM, 16, true, WIDE>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
-        wino_phase_body<2, 2, false, GEOM, 16, true, WIDE>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
+        wino_phase_body<3, 3, false, GEOM, SC, false, WIDE>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
+        wino_phase_body<3, 2, false, GEOM, SC, true, WIDE>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
+        wino_phase_body<3, 2, true, GEOM, SC, true, WIDE>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
+        wino_phase_body<2, 2, false, GEOM, SC, true, WIDE>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
     } else {
         constexpr bool W = WIDE;        // (false here: the chained form)
-        wino_phase_body<3, 3, false, GEOM, 16, false, W, W ? 0 : 2, 3, 2>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, U4[2], 1, 0, ub);
-        wino_phase_body<3, 2, false, GEOM, 16, true, W, W ? 0 : 3, 3, 2>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ub, U4[1], 0, 1, ua);
-        wino_phase_body<3, 2, true, GEOM, 16, true, W, W ? 0 : 3, 2, 2>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, U4[0], 0, 0, ub);
-        wino_phase_body<2, 2, false, GEOM, 16, true, W, W ? 0 : 1>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ub, nullptr, 0, 0, ua);
+        if (!W) wino_first_stage(a, 1, 1, fill, lds);
+        wino_phase_body<3, 3, false, GEOM, SC, false, W, W ? 0 : 3, 3, 2>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, U4[2], 1, 0, ub);
+        wino_phase_body<3, 2, false, GEOM, SC, true, W, W ? 0 : 3, 3, 2>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ub, U4[1], 0, 1, ua);
+        wino_phase_body<3, 2, true, GEOM, SC, true, W, W ? 0 : 3, 2, 2>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, U4[0], 0, 0, ub);
+        wino_phase_body<2, 2, false, GEOM, SC, true, W, W ? 0 : 1>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ub, nullptr, 0, 0, ua);
     }
     wino_store_block<GEOM, WIDE ? 256 : 512>(a, 3, wb, xch);
 }
 
-template <int GEOM, bool WIDE>
+template <int GEOM, bool WIDE, int STAGE_CH = 16>
 __global__ __launch_bounds__(WIDE ? 256 : 512) void conv_wino_layer_kernel(ConvWinoLayerArgs p) {
     AAE_DYN_SMEM(smem_raw);
     const ConvWinoArgs& a = p.c;
     const WinoBlock wb = wino_block<GEOM>(blockIdx.x, a.Cout / 64, a.blocks_x, a.blocks_y, a.regions, a.xcd_cols);
     if (!wb.live) return;
-    wino_layer_block<GEOM, WIDE>(a, p.U4, wb, smem_raw);
+    wino_layer_block<GEOM, WIDE, STAGE_CH>(a, p.U4, wb, smem_raw);
 #ifdef AAE_WINO_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     AAE_WINO_STAMP(a, 16);
@@ -720,7 +796,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 512) void conv_wino_layer_kernel(ConvW
 
 // ---- the same launch over several objects (ConvWinoMultiArgs): a block finds the object its region belongs to and runs exactly the
 //      single-object block on that object's tensors -- bit-identical to the object's own launch.
-template <int GEOM>
+template <int GEOM, int STAGE_CH = 16>
 __global__ __launch_bounds__(512) void conv_wino_layer_multi_kernel(ConvWinoMultiArgs p) {
     AAE_DYN_SMEM(smem_raw);
     WinoBlock wb;
@@ -732,7 +808,7 @@ __global__ __launch_bounds__(512) void conv_wino_layer_multi_kernel(ConvWinoMult
     const ConvWinoObject& ob = p.obj[o];
     a.x = ob.x; a.out = ob.out; a.bias = ob.bias; a.bn_scale = ob.bn_scale; a.bn_shift = ob.bn_shift; a.B = ob.B;
     const float* U4[4] = {ob.U4[0], ob.U4[1], ob.U4[2], ob.U4[3]};
-    wino_layer_block<GEOM, false>(a, U4, wb, smem_raw);
+    wino_layer_block<GEOM, false, STAGE_CH>(a, U4, wb, smem_raw);
 }
 
 #endif  // AAE_WINO_DECLARATIONS_ONLY
