@@ -16,7 +16,7 @@ AAE_DTYPE_F32 = 1
 AAE_DTYPE_BF16 = 2
 AAE_MAX_LAYERS = 8
 AAE_SCAN_AUTO, AAE_SCAN_GEMV, AAE_SCAN_MFMA, AAE_SCAN_STREAM, AAE_SCAN_STREAM_2L, AAE_SCAN_AUTO_NO_PRUNE, AAE_SCAN_STREAM_WALK = 0, 1, 2, 3, 4, 5, 6
-AAE_SCAN_AUTO_PACKED, AAE_SCAN_AUTO_RH2, AAE_SCAN_AUTO_FIN = 7, 8, 9
+AAE_SCAN_AUTO_PACKED, AAE_SCAN_AUTO_RH2, AAE_SCAN_AUTO_FIN, AAE_SCAN_AUTO_TOPK_ROWS = 7, 8, 9, 10
 AAE_ABI_VERSION = 3
 
 LIB_NAME = 'libaae_hip.so'
@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     'aae_encoder_split_precision_for_batch',
     'aae_codebook_create', 'aae_codebook_update', 'aae_codebook_destroy', 'aae_codebook_set_scan_mode',
     'aae_codebook_prepare_upright',
-    'aae_codebook_workspace_bytes', 'aae_codebook_nn', 'aae_codebook_nn_timed', 'aae_encode_nn', 'aae_detect_nn', 'aae_codebook_similarity', 'aae_l2_normalize',
+    'aae_codebook_workspace_bytes', 'aae_codebook_nn', 'aae_codebook_nn_timed', 'aae_codebook_last_launches', 'aae_encode_nn', 'aae_encode_nn_topk', 'aae_detect_nn', 'aae_codebook_similarity', 'aae_l2_normalize',
     'aae_crop_resize_u8', 'aae_pack_pairs', 'aae_unpack_pairs',
     'aae_multi_workspace_bytes', 'aae_multi_rows', 'aae_encode_nn_multi', 'aae_codebook_nn_multi', 'aae_detect_nn_multi', 'aae_multi_last_launches',
     'aae_decoder_create', 'aae_decoder_destroy', 'aae_decoder_workspace_bytes', 'aae_decoder_forward',
@@ -137,6 +137,11 @@ def declare(lib):
     lib.aae_encode_nn.restype = c_int
     lib.aae_encode_nn.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p, c_size_t, c_void_p]
+    lib.aae_encode_nn_topk.restype = c_int
+    lib.aae_encode_nn_topk.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p, c_size_t, c_void_p]
+    lib.aae_codebook_last_launches.restype = c_int
+    lib.aae_codebook_last_launches.argtypes = []
     lib.aae_codebook_nn.restype = c_int
     lib.aae_codebook_nn.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.aae_codebook_nn_timed.restype = c_int

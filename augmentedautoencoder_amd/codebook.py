@@ -6,6 +6,7 @@ ignored (may be None)."""
 from __future__ import annotations
 
 import ast
+import inspect
 
 import numpy as np
 
@@ -153,20 +154,26 @@ class Codebook(object):
         callers below derive further device results from z), in exact fp32 -- the default -- settle() is a no-op."""
         return self._encoder.engine.encode_checked(self._prep(x))
 
-    def _encode_nn_host(self, x, stride):
-        """fused encoder + top-1 scan -> indices on the host; the range flag rides along with the result copy"""
+    def _encode_nn_host(self, x, stride, top_n=1, with_scores=False):
+        """fused encoder + scan (top-1, or the top_n best) -> indices [B,top_n] (and cosines) on the host; the range flag rides
+        along with the result copy"""
         eng = self._encoder.engine
-        _, idx, _ = eng.encode_nn(self.engine, self._prep(x), stride)
-        idcs = idx[:, 0].cpu().numpy()
+        if top_n == 1:
+            _, idx, score = eng.encode_nn(self.engine, self._prep(x), stride)
+        elif 'topk' in inspect.signature(eng.encode_nn).parameters:
+            _, idx, score = eng.encode_nn(self.engine, self._prep(x), stride, topk=int(top_n))
+        else:                                 # an injected engine with the top-1-only encode_nn: its two calls (same kernels, same bits)
+            idx, score = self.engine.nn(eng.encode_checked(self._prep(x)), int(top_n), stride)
+        idcs, scores = idx.cpu().numpy(), (score.cpu().numpy() if with_scores else None)
         if eng.settle():                      # (split precision, out of range: recomputed in exact fp32, in place)
-            idcs = idx[:, 0].cpu().numpy()
-        return idcs
+            idcs, scores = idx.cpu().numpy(), (score.cpu().numpy() if with_scores else None)
+        return (idcs, scores) if with_scores else idcs
 
     def _run_similarity(self, feed):
         return self.engine.similarity(self._encode(self._encoder._feed(feed))).cpu().numpy()
 
     def _run_argmax(self, feed):
-        return self._encode_nn_host(self._encoder._feed(feed), 1)
+        return self._encode_nn_host(self._encoder._feed(feed), 1)[:, 0]
 
     def _run_query(self, feed, normalized):
         z = self._encode(self._encoder._feed(feed))
@@ -180,22 +187,25 @@ class Codebook(object):
         if top_n == 1:
             # encoder + scan in one C call (aae_encode_nn): per detection that is six launches
             stride = int(self._dataset._kw['num_cyclo']) if upright else 1
-            idcs = self._encode_nn_host(x, stride)
+            idcs = self._encode_nn_host(x, stride)[:, 0]
         else:
-            z = self._encode(x)
-            if z.shape[0] != 1:
+            x = self._prep(x)
+            n = x.shape[0] if hasattr(x, 'shape') else len(x)
+            if n != 1:
                 # the reference squeezes the [B,N] similarity (codebook.py:70): only B == 1 is meaningful
-                raise ValueError('top_n > 1 needs a single crop (got a batch of %d)' % z.shape[0])
-            idx, _ = self.engine.nn(z, int(top_n), 1)
-            idcs = idx[0].cpu().numpy()
+                raise ValueError('top_n > 1 needs a single crop (got a batch of %d)' % n)
+            # ... and likewise one C call (aae_encode_nn_topk): the scan keeps sorted lists per block and answers inside its launch
+            idcs = self._encode_nn_host(x, 1, int(top_n))[0]
         if return_idcs:
             return idcs
         return self._dataset.viewsphere_for_embedding[idcs].squeeze()
 
     def nearest_rotation_with_scores(self, x, top_n=1, upright=False):
         """Extension: (indices, cosine scores) without materialising the similarity."""
-        z = self._encode(x)
         stride = int(self._dataset._kw['num_cyclo']) if (upright and top_n == 1) else 1
+        if top_n > 1:                         # one fused C call (aae_encode_nn_topk)
+            return self._encode_nn_host(x, 1, int(top_n), with_scores=True)
+        z = self._encode(x)
         idx, score = self.engine.nn(z, int(top_n), stride)
         return idx.cpu().numpy(), score.cpu().numpy()
 

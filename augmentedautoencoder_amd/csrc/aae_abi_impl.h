@@ -538,6 +538,7 @@ int aae_codebook_prepare_upright(aae_codebook* cb, int col_stride, void* stream_
         }
         sub->scan_mode = cb->scan_mode; sub->scan_ticket = cb->scan_ticket; sub->topk_prune = cb->topk_prune; sub->cu_count = cb->cu_count;
         sub->scan_walk = cb->scan_walk; sub->scan_fused_norm = cb->scan_fused_norm; sub->scan_rh4 = cb->scan_rh4; sub->scan_resident_fin = cb->scan_resident_fin;
+        sub->scan_topk_stream = cb->scan_topk_stream;
         cb->upright = sub; cb->upright_stride = col_stride;
     }
     if (int rc = gather_upright_rows(cb, cb->upright, cb->upright_stride, stream)) return rc;
@@ -568,7 +569,7 @@ int aae_codebook_set_scan_mode(aae_codebook* cb, int mode) {
     using namespace aae_host;
     if (!cb) return fail(AAE_ERR_INVALID, "aae_codebook_set_scan_mode: null handle");
     if (mode != AAE_SCAN_AUTO && mode != AAE_SCAN_GEMV && mode != AAE_SCAN_MFMA && mode != AAE_SCAN_STREAM && mode != AAE_SCAN_STREAM_2L &&
-        mode != AAE_SCAN_AUTO_NO_PRUNE && mode != AAE_SCAN_STREAM_WALK && mode != AAE_SCAN_AUTO_PACKED && mode != AAE_SCAN_AUTO_RH2 && mode != AAE_SCAN_AUTO_FIN)
+        mode != AAE_SCAN_AUTO_NO_PRUNE && mode != AAE_SCAN_STREAM_WALK && mode != AAE_SCAN_AUTO_PACKED && mode != AAE_SCAN_AUTO_RH2 && mode != AAE_SCAN_AUTO_FIN && mode != AAE_SCAN_AUTO_TOPK_ROWS)
         return fail(AAE_ERR_INVALID, "scan mode %d", mode);
 #ifndef AAE_EXPERIMENTS
     if (mode == AAE_SCAN_GEMV || mode == AAE_SCAN_STREAM_WALK)
@@ -580,17 +581,20 @@ int aae_codebook_set_scan_mode(aae_codebook* cb, int mode) {
     cb->scan_fused_norm = mode == AAE_SCAN_AUTO_PACKED ? 0 : 1;
     cb->scan_rh4 = mode == AAE_SCAN_AUTO_RH2 ? 0 : 1;
     cb->scan_resident_fin = mode == AAE_SCAN_AUTO_FIN ? 1 : 0;
+    cb->scan_topk_stream = mode == AAE_SCAN_AUTO_TOPK_ROWS ? 0 : 1;
     cb->scan_mode = (mode == AAE_SCAN_STREAM_2L || mode == AAE_SCAN_STREAM_WALK) ? AAE_SCAN_STREAM
-                    : ((mode == AAE_SCAN_AUTO_NO_PRUNE || mode == AAE_SCAN_AUTO_PACKED || mode == AAE_SCAN_AUTO_RH2 || mode == AAE_SCAN_AUTO_FIN) ? AAE_SCAN_AUTO : mode);
+                    : ((mode == AAE_SCAN_AUTO_NO_PRUNE || mode == AAE_SCAN_AUTO_PACKED || mode == AAE_SCAN_AUTO_RH2 || mode == AAE_SCAN_AUTO_FIN || mode == AAE_SCAN_AUTO_TOPK_ROWS) ? AAE_SCAN_AUTO : mode);
     for (auto& c : cb->upright_copies) {
         c.second->scan_mode = cb->scan_mode; c.second->scan_ticket = cb->scan_ticket; c.second->topk_prune = cb->topk_prune; c.second->scan_walk = cb->scan_walk;
         c.second->scan_fused_norm = cb->scan_fused_norm; c.second->scan_rh4 = cb->scan_rh4; c.second->scan_resident_fin = cb->scan_resident_fin;
+        c.second->scan_topk_stream = cb->scan_topk_stream;
     }
     return AAE_OK;
 }
 
 size_t aae_codebook_workspace_bytes(const aae_codebook* cb, int B, int topk) {
     if (!cb || B < 1 || topk < 1) return 0;
+    if (topk > 1) return aae_host::plan_scan(cb, B, topk).total;                                               // (no upright top-k: codebook.py:65-66)
     return std::max(aae_host::plan_scan(cb, B, topk).total, aae_host::plan_scan(cb, B, topk, true).total);    // (with or without a masked upright query)
 }
 
@@ -598,13 +602,14 @@ size_t aae_codebook_workspace_bytes(const aae_codebook* cb, int B, int topk) {
 static int nn_impl(aae_codebook* cb, const float* z, int B, int topk, int col_stride, int64_t* idx_out,
                    float* score_out, void* workspace, size_t ws_bytes, void* stream_v, unsigned prepared_nonce) {
     using namespace aae_host;
+    t_cb_launches = 0;
     if (!cb || !z || !idx_out || !score_out) return fail(AAE_ERR_INVALID, "aae_codebook_nn: null argument");
     if (B < 1 || topk < 1 || topk > cb->N) return fail(AAE_ERR_INVALID, "aae_codebook_nn: B=%d topk=%d N=%d", B, topk, cb->N);
     if (col_stride < 1) return fail(AAE_ERR_INVALID, "col_stride %d < 1", col_stride);
     if (topk > 1 && col_stride != 1) return fail(AAE_ERR_INVALID, "upright (col_stride>1) is defined for topk == 1 only (codebook.py:65-66)");
     if (topk > 1 && B > 65535) return fail(AAE_ERR_UNSUPPORTED, "top-k for more than 65535 queries per call (got %d): split the batch", B);
     {
-        const size_t need = std::max(plan_scan(cb, B, topk).total, plan_scan(cb, B, topk, true).total);
+        const size_t need = aae_codebook_workspace_bytes(cb, B, topk);
         if (ws_bytes < need) return fail(AAE_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
     }
     if (!workspace || ((uintptr_t)workspace & 255)) return fail(AAE_ERR_WORKSPACE, "workspace must be non-null and 256-B aligned");
@@ -625,25 +630,27 @@ static int nn_impl(aae_codebook* cb, const float* z, int B, int topk, int col_st
     fin.idx_out = idx_out; fin.score_out = score_out; fin.idx_scale = idx_scale; fin.nonce = prepared_nonce;
     // (opt-in, AAE_SCAN_AUTO_FIN: the same for the query-resident scan of at most 32 queries -- one row of row blocks)
     const bool resident_fin = topk == 1 && cb->scan_resident_fin && s.resident_ok && ceil_div(s.Bpad, 256 / s.res_rh) == 1 && col_stride == 1;
-    const bool one_launch = topk == 1 && ((s.stream && cb->scan_ticket != 0) || resident_fin);
-    if (int rc = run_scan(cb, z, B, col_stride, cs, s, base, stream, &partial_rows, one_launch ? &fin : nullptr, s.topk_fused ? topk : 1)) return rc;
-    if (one_launch) return AAE_OK;
+    // ... and top-k 2 ... 8 likewise: the blocks leave sorted lists, the last one merges them (AAE_SCAN_STREAM_2L: a merge launch behind the scan)
+    fin.in_launch = !s.topk_stream || cb->scan_ticket != 0;
+    const bool one_launch = (topk == 1 && ((s.stream && cb->scan_ticket != 0) || resident_fin)) || (s.topk_stream && fin.in_launch);
+    if (int rc = run_scan(cb, z, B, col_stride, cs, s, base, stream, &partial_rows, (one_launch || s.topk_stream) ? &fin : nullptr, s.topk_fused ? topk : 1)) return rc;
+    if (one_launch || s.topk_stream) return AAE_OK;
     if (topk == 1) {
         aae::ArgmaxReduceArgs r;
         r.pval = reinterpret_cast<float*>(base + s.pval_off);
         r.pidx = reinterpret_cast<int*>(base + s.pidx_off);
         r.idx_out = reinterpret_cast<long long*>(idx_out);
         r.score_out = score_out; r.nblk = partial_rows; r.B = B; r.Bstride = s.Bstride; r.idx_scale = idx_scale;
-        AAE_LAUNCH((aae::argmax_reduce_kernel), dim3(B), dim3(256), 64, stream, r);
+        AAE_CB_LAUNCH((aae::argmax_reduce_kernel), dim3(B), dim3(256), 64, stream, r);
     } else {
         aae::TopKArgs t;
         t.cs = cs; t.idx_out = reinterpret_cast<long long*>(idx_out); t.score_out = score_out; t.N = cb->N; t.k = topk;
         t.chunks = s.cand_chunks;
         t.cand_v = reinterpret_cast<float*>(base + s.cand_off);
         t.cand_i = reinterpret_cast<int*>(base + s.cand_off + align_up((size_t)B * t.chunks * topk * sizeof(float), 256));
-        if (!s.topk_fused) AAE_LAUNCH((aae::topk_chunks_kernel), dim3(t.chunks, B), dim3(256), 64, stream, t);   // (fused: the scan wrote the lists)
-        if (t.chunks * topk <= 256 * aae::kTopKMergeSlots) AAE_LAUNCH((aae::topk_merge_kernel<true>), dim3(B), dim3(256), 64, stream, t);
-        else AAE_LAUNCH((aae::topk_merge_kernel<false>), dim3(B), dim3(256), 64, stream, t);
+        if (!s.topk_fused) AAE_CB_LAUNCH((aae::topk_chunks_kernel), dim3(t.chunks, B), dim3(256), 64, stream, t);   // (fused: the scan wrote the lists)
+        if (t.chunks * topk <= 256 * aae::kTopKMergeSlots) AAE_CB_LAUNCH((aae::topk_merge_kernel<true>), dim3(B), dim3(256), 64, stream, t);
+        else AAE_CB_LAUNCH((aae::topk_merge_kernel<false>), dim3(B), dim3(256), 64, stream, t);
     }
     AAE_HIP_TRY(hipGetLastError());
     return AAE_OK;
@@ -712,10 +719,37 @@ int aae_encode_nn(aae_encoder* enc, aae_codebook* cb, const void* x, int x_dtype
     }
     bool prepared = false, scan_done = false;
     Timer tm;
+    t_cb_launches = 0;                                   // (the persistent launch, when it runs, carries the scan as its last phase)
     if (int rc = forward_impl(enc, x, x_dtype, B, z_out, enc_workspace, enc_ws_bytes, stream, tm, extra.words ? &extra : nullptr, &prepared, &scan_done)) return rc;
     if (scan_done) return AAE_OK;
     return nn_impl(cb, z_out, B, 1, col_stride, idx_out, score_out, cb_workspace, cb_ws_bytes, stream, prepared ? extra.nonce : 0u);
 }
+
+int aae_encode_nn_topk(aae_encoder* enc, aae_codebook* cb, const void* x, int x_dtype, int B, int topk, float* z_out,
+                       int64_t* idx_out, float* score_out, void* enc_workspace, size_t enc_ws_bytes, void* cb_workspace,
+                       size_t cb_ws_bytes, void* stream) {
+    using namespace aae_host;
+    if (!enc || !cb) return fail(AAE_ERR_INVALID, "aae_encode_nn_topk: null handle");
+    if (topk < 1) return fail(AAE_ERR_INVALID, "aae_encode_nn_topk: topk %d < 1", topk);
+    if (topk == 1) return aae_encode_nn(enc, cb, x, x_dtype, B, 1, z_out, idx_out, score_out, enc_workspace, enc_ws_bytes, cb_workspace, cb_ws_bytes, stream);
+    if (!cb_workspace || ((uintptr_t)cb_workspace & 255)) return fail(AAE_ERR_WORKSPACE, "workspace must be non-null and 256-B aligned");
+    if (B >= 1 && cb_ws_bytes < aae_codebook_workspace_bytes(cb, B, topk)) return fail(AAE_ERR_WORKSPACE, "codebook workspace %zu B too small", cb_ws_bytes);
+    t_cb_launches = 0;
+    // B <= 4, top-k 2 ... 8: the scan merges its blocks' lists inside its own launch; as for top-1 its ticket words (front of the
+    // codebook workspace) are prepared by the encoder's first kernel.  (The persistent per-detection launch answers top-1 only.)
+    ExtraTicketPrep extra;
+    if (B >= 1 && cb->scan_ticket >= 1 && plan_scan(cb, B, topk).topk_stream) {
+        extra.words = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(cb_workspace) + plan_scan(cb, B, topk).ticket_off);
+        extra.count = aae::kTicketSlotWords;
+        extra.nonce = next_nonce();
+    }
+    bool prepared = false, scan_done = false;
+    Timer tm;
+    if (int rc = forward_impl(enc, x, x_dtype, B, z_out, enc_workspace, enc_ws_bytes, stream, tm, extra.words ? &extra : nullptr, &prepared, &scan_done)) return rc;
+    return nn_impl(cb, z_out, B, topk, 1, idx_out, score_out, cb_workspace, cb_ws_bytes, stream, prepared ? extra.nonce : 0u);
+}
+
+int aae_codebook_last_launches(void) { return aae_host::t_cb_launches; }
 
 int aae_codebook_similarity(aae_codebook* cb, const float* z, int B, float* cs_out, void* workspace, size_t ws_bytes,
                             void* stream_v) {

@@ -6,12 +6,17 @@
 namespace aae_host {
 
 // --------------------------------------------------------------- codebook side
+// kernel launches the calling thread's last codebook query queued (aae_codebook_last_launches)
+static thread_local int t_cb_launches = 0;
+#define AAE_CB_LAUNCH(...) do { ++aae_host::t_cb_launches; AAE_LAUNCH(__VA_ARGS__); } while (0)
+
 struct ScanPlan {
     int nblk, Bpad, Bstride, Jpad, NT;
     bool gemv, stream;
     bool resident_ok;              // query-resident streaming kernel eligible (top-1, no similarity output, stride 1 decided at run time)
     int res_tiles_per_block, res_blocks, res_rh;
-    bool topk_fused;               // top-k (2..8) inside the query-resident kernel: no [B][N] similarity matrix
+    bool topk_fused;               // top-k (2..8) inside the scan (query-resident kernel, or the B <= 4 stream kernels): no [B][N] similarity matrix
+    bool topk_stream;              // ... inside the stream kernels: sorted lists per block, merged by the last block to arrive (or scan_topk_merge_lists_kernel)
     int cand_chunks;               // candidate lists per query that topk_merge_kernel merges
     size_t ticket_off, q_off, qp_off, pval_off, pidx_off, cs_off, cand_off, prune_off, total;
 };
@@ -22,12 +27,19 @@ struct ScanTicketOut {
     float* score_out = nullptr;
     int idx_scale = 1;
     unsigned nonce = 0;            // != 0: the ticket words were prepared with this nonce by an earlier kernel on the stream
+    bool in_launch = true;         // false (top-k on a stream kernel under AAE_SCAN_STREAM_2L): the answers come from a merge launch behind the scan
 };
 
 // masked: an upright query (col_stride > 1) WITHOUT a prepared compacted copy (aae_codebook_prepare_upright) -- every row is
 // scanned and the rows off the stride are masked out.  The product build runs that rare form on the tile-resident kernels at
 // every batch size (the masked variants of the stream kernels: experiments build); with the copy an upright query is an ordinary
 // stride-1 scan of N / col_stride rows.
+// bytes of one block's list for one query in the stream kernels' top-k: the smallest instantiated K >= k slots (launch_scan_stream_k)
+static size_t scan_list_bytes(int topk) {
+    const int K = topk <= 2 ? 2 : (topk <= 4 ? 4 : (topk == 5 ? 5 : 8));
+    return (size_t)aae::scan_list_entries(K) * 8;
+}
+
 static ScanPlan plan_scan(const aae_codebook* cb, int B, int topk, bool masked = false) {
     ScanPlan s;
 #ifdef AAE_EXPERIMENTS
@@ -67,7 +79,9 @@ static ScanPlan plan_scan(const aae_codebook* cb, int B, int topk, bool masked =
         s.resident_ok = s.res_blocks <= s.nblk;          // the partial buffers are sized for nblk row blocks
     }
     // top-k (2 <= k <= 8) on the query-resident kernel: per-lane sorted lists instead of the [B][N] similarity matrix
-    s.topk_fused = topk >= 2 && topk <= 8 && s.resident_ok;     // (AAE_SCAN_MFMA keeps the similarity-matrix path for A/B)
+    // ... and on the B <= 4 stream kernels: a sorted list per block and query (AAE_SCAN_AUTO_TOPK_ROWS keeps the similarity rows for A/B)
+    s.topk_stream = topk >= 2 && topk <= 8 && s.stream && cb->scan_topk_stream != 0 && !cb->scan_walk;
+    s.topk_fused = topk >= 2 && topk <= 8 && (s.resident_ok || s.topk_stream);     // (AAE_SCAN_MFMA keeps the similarity-matrix path for A/B)
     size_t off = 0;
     s.ticket_off = off; off += align_up((size_t)aae::kTicketSlotWords * 8, 256);   // block_ticket_arrive words of the single-launch stream scan
     s.q_off = off;    off += align_up((size_t)B * cb->J * sizeof(float), 256);
@@ -81,7 +95,8 @@ static ScanPlan plan_scan(const aae_codebook* cb, int B, int topk, bool masked =
     if (topk > 1 && !s.topk_fused) off += align_up((size_t)B * cb->N * sizeof(float), 256);
     s.cand_off = off;
     s.cand_chunks = s.topk_fused ? s.res_blocks : ceil_div(cb->N, aae::kTopKChunk);
-    if (topk > 1) off += 2 * align_up((size_t)B * s.cand_chunks * topk * sizeof(float), 256);
+    if (s.topk_stream) off += align_up((size_t)partial_rows * B * scan_list_bytes(topk), 256);     // [block][query] lists, rows as for the partials
+    else if (topk > 1) off += 2 * align_up((size_t)B * s.cand_chunks * topk * sizeof(float), 256);
     s.prune_off = off;                                  // shared bound words of the pruned top-k scan
     if (s.topk_fused) off += align_up((size_t)aae::kPruneReplicas * s.Bpad * aae::kPruneGroups * sizeof(int), 256);
     s.total = off;
@@ -93,10 +108,10 @@ static void launch_scan_mfma_t(const aae::ScanArgs& a, bool upright, int nblk, h
     constexpr int smem = aae::scan_mfma_smem<NT>();
     if (upright) {
         (void)hipFuncSetAttribute((const void*)aae::scan_mfma_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::scan_mfma_kernel<NT, true>), dim3(nblk), dim3(256), smem, stream, a);
+        AAE_CB_LAUNCH((aae::scan_mfma_kernel<NT, true>), dim3(nblk), dim3(256), smem, stream, a);
     } else {
         (void)hipFuncSetAttribute((const void*)aae::scan_mfma_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::scan_mfma_kernel<NT, false>), dim3(nblk), dim3(256), smem, stream, a);
+        AAE_CB_LAUNCH((aae::scan_mfma_kernel<NT, false>), dim3(nblk), dim3(256), smem, stream, a);
     }
 }
 
@@ -107,25 +122,50 @@ static void launch_scan_stream_t(const aae::ScanArgs& a, bool upright, int nblk,
     const int smem = NQ * 128 * (int)sizeof(float) + aae::kScanTicketSmem;
 #ifdef AAE_EXPERIMENTS
     if (upright) {
-        if (a.cs) AAE_LAUNCH((aae::scan_stream_kernel<NQ, true, true>), dim3(nblk), dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::scan_stream_kernel<NQ, true, false>), dim3(nblk), dim3(256), smem, stream, a);
+        if (a.cs) AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, true, true>), dim3(nblk), dim3(256), smem, stream, a);
+        else AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, true, false>), dim3(nblk), dim3(256), smem, stream, a);
         return;
     }
 #endif
     (void)upright;                              // (product build: plan_scan never sends a masked query here)
-    if (a.cs) AAE_LAUNCH((aae::scan_stream_kernel<NQ, false, true>), dim3(nblk), dim3(256), smem, stream, a);
-    else AAE_LAUNCH((aae::scan_stream_kernel<NQ, false, false>), dim3(nblk), dim3(256), smem, stream, a);
+    if (a.cs) AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, true>), dim3(nblk), dim3(256), smem, stream, a);
+    else AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, false>), dim3(nblk), dim3(256), smem, stream, a);
+}
+// top-k 2 ... 8 inside the stream scan: list slots = the smallest instantiated K >= k (the set of launch_scan_resident_k)
+template <int NQ>
+static void launch_scan_stream_k(const aae::ScanArgs& a, int nblk, hipStream_t stream) {
+    const int smem = NQ * 128 * (int)sizeof(float) + aae::kScanTicketSmem;
+    if (a.k <= 2) AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, false, 2>), dim3(nblk), dim3(256), smem, stream, a);
+    else if (a.k <= 4) AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, false, 4>), dim3(nblk), dim3(256), smem, stream, a);
+    else if (a.k == 5) AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, false, 5>), dim3(nblk), dim3(256), smem, stream, a);
+    else AAE_CB_LAUNCH((aae::scan_stream_kernel<NQ, false, false, 8>), dim3(nblk), dim3(256), smem, stream, a);
+}
+template <int NQ>
+static void launch_scan_stream_bf16_k(const aae::ScanArgs& a, int nblk, hipStream_t stream) {
+    const int smem = NQ * 256 * (int)sizeof(float) + aae::kScanTicketSmem;
+    if (a.k <= 2) AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false, 2>), dim3(nblk), dim3(256), smem, stream, a);
+    else if (a.k <= 4) AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false, 4>), dim3(nblk), dim3(256), smem, stream, a);
+    else if (a.k == 5) AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false, 5>), dim3(nblk), dim3(256), smem, stream, a);
+    else AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false, 8>), dim3(nblk), dim3(256), smem, stream, a);
+}
+// the merge of the blocks' lists as a launch of its own (no in-launch finish: AAE_SCAN_STREAM_2L)
+static void launch_scan_topk_merge_lists(const aae::ScanArgs& a, int nblk, hipStream_t stream) {
+    const int smem = 4 * 4 * 8 * (int)sizeof(uint32_t);
+    if (a.k <= 2) AAE_CB_LAUNCH((aae::scan_topk_merge_lists_kernel<2>), dim3(1), dim3(256), smem, stream, a, nblk);
+    else if (a.k <= 4) AAE_CB_LAUNCH((aae::scan_topk_merge_lists_kernel<4>), dim3(1), dim3(256), smem, stream, a, nblk);
+    else if (a.k == 5) AAE_CB_LAUNCH((aae::scan_topk_merge_lists_kernel<5>), dim3(1), dim3(256), smem, stream, a, nblk);
+    else AAE_CB_LAUNCH((aae::scan_topk_merge_lists_kernel<8>), dim3(1), dim3(256), smem, stream, a, nblk);
 }
 #ifdef AAE_EXPERIMENTS
 template <int NQ>
 static void launch_scan_walk_t(const aae::ScanArgs& a, bool upright, int blocks, hipStream_t stream) {
     const int smem = 8 * NQ * (int)sizeof(float) + aae::kScanTicketSmem;
     if (a.cs) {
-        if (upright) AAE_LAUNCH((aae::scan_stream_walk_kernel<NQ, true, true>), dim3(blocks), dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::scan_stream_walk_kernel<NQ, false, true>), dim3(blocks), dim3(256), smem, stream, a);
+        if (upright) AAE_CB_LAUNCH((aae::scan_stream_walk_kernel<NQ, true, true>), dim3(blocks), dim3(256), smem, stream, a);
+        else AAE_CB_LAUNCH((aae::scan_stream_walk_kernel<NQ, false, true>), dim3(blocks), dim3(256), smem, stream, a);
     } else {
-        if (upright) AAE_LAUNCH((aae::scan_stream_walk_kernel<NQ, true, false>), dim3(blocks), dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::scan_stream_walk_kernel<NQ, false, false>), dim3(blocks), dim3(256), smem, stream, a);
+        if (upright) AAE_CB_LAUNCH((aae::scan_stream_walk_kernel<NQ, true, false>), dim3(blocks), dim3(256), smem, stream, a);
+        else AAE_CB_LAUNCH((aae::scan_stream_walk_kernel<NQ, false, false>), dim3(blocks), dim3(256), smem, stream, a);
     }
 }
 #endif
@@ -134,21 +174,21 @@ static void launch_scan_stream_bf16_t(const aae::ScanArgs& a, bool upright, int 
     const int smem = NQ * 256 * (int)sizeof(float) + aae::kScanTicketSmem;
 #ifdef AAE_EXPERIMENTS
     if (upright) {
-        if (a.cs) AAE_LAUNCH((aae::scan_stream_bf16_kernel<NQ, true, true>), dim3(nblk), dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::scan_stream_bf16_kernel<NQ, true, false>), dim3(nblk), dim3(256), smem, stream, a);
+        if (a.cs) AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, true, true>), dim3(nblk), dim3(256), smem, stream, a);
+        else AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, true, false>), dim3(nblk), dim3(256), smem, stream, a);
         return;
     }
 #endif
     (void)upright;
-    if (a.cs) AAE_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, true>), dim3(nblk), dim3(256), smem, stream, a);
-    else AAE_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false>), dim3(nblk), dim3(256), smem, stream, a);
+    if (a.cs) AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, true>), dim3(nblk), dim3(256), smem, stream, a);
+    else AAE_CB_LAUNCH((aae::scan_stream_bf16_kernel<NQ, false, false>), dim3(nblk), dim3(256), smem, stream, a);
 }
 
 template <bool BF16, int K, int RH, bool NORM = false>
 static void launch_scan_resident_t(const aae::ScanResidentArgs& a, dim3 grid, hipStream_t stream) {
     constexpr int smem = aae::scan_resident_smem<BF16, RH>();
     (void)hipFuncSetAttribute((const void*)aae::scan_resident_kernel<BF16, K, RH, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    AAE_LAUNCH((aae::scan_resident_kernel<BF16, K, RH, NORM>), grid, dim3(aae::kScanResidentThreads), smem, stream, a);
+    AAE_CB_LAUNCH((aae::scan_resident_kernel<BF16, K, RH, NORM>), grid, dim3(aae::kScanResidentThreads), smem, stream, a);
 }
 template <bool BF16, int RH>
 static void launch_scan_resident_k(const aae::ScanResidentArgs& a, dim3 grid, hipStream_t stream) {
@@ -202,6 +242,15 @@ static int launch_scan_resident(const aae_codebook* cb, const void* qp, int B, c
     return AAE_OK;
 }
 
+// top-k inside a stream scan: where the blocks' lists go and where the merge (in-launch with fin, else a launch behind the scan) answers
+static void scan_topk_args(aae::ScanArgs& a, const ScanPlan& s, unsigned char* base, int topk, const ScanTicketOut& fin) {
+    a.cand = reinterpret_cast<float*>(base + s.cand_off);
+    a.k = topk;
+    a.cs = nullptr;
+    a.idx_out = reinterpret_cast<long long*>(fin.idx_out); a.score_out = fin.score_out; a.idx_scale = fin.idx_scale;
+    if (!fin.in_launch) { a.tickets = nullptr; a.nonce = 0; }
+}
+
 // *partial_rows: how many [Bstride]-rows of (pval, pidx) the arg-max reduce has to look at
 static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, float* cs_out, const ScanPlan& s,
                     unsigned char* base, hipStream_t stream, int* partial_rows = nullptr, const ScanTicketOut* fin = nullptr, int topk = 1) {
@@ -226,6 +275,13 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
             a.idx_out = reinterpret_cast<long long*>(fin->idx_out); a.score_out = fin->score_out; a.idx_scale = fin->idx_scale;
         }
         const bool up = col_stride > 1;
+        if (s.topk_stream && topk > 1 && fin) {             // sorted lists per block instead of the arg-max partials
+            scan_topk_args(a, s, base, topk, *fin);
+            if (B == 1) launch_scan_stream_bf16_k<1>(a, s.nblk, stream);
+            else if (B == 2) launch_scan_stream_bf16_k<2>(a, s.nblk, stream);
+            else launch_scan_stream_bf16_k<4>(a, s.nblk, stream);
+            if (!a.tickets) launch_scan_topk_merge_lists(a, s.nblk, stream);
+        } else
         if (B == 1) launch_scan_stream_bf16_t<1>(a, up, s.nblk, stream);
         else if (B == 2) launch_scan_stream_bf16_t<2>(a, up, s.nblk, stream);
         else launch_scan_stream_bf16_t<4>(a, up, s.nblk, stream);
@@ -236,7 +292,7 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
         aae::L2NormBf16Args n;
         n.z = z; n.qp3 = reinterpret_cast<unsigned short*>(qp); n.B = B; n.J = cb->J; n.Jpad = 128; n.Bpad = s.Bpad;
         if (resident && topk > 1 && cb->topk_prune) n.prune = reinterpret_cast<int*>(base + s.prune_off);
-        AAE_LAUNCH((aae::l2norm_pack_bf16x3_kernel), dim3(ceil_div(s.Bpad, 4)), dim3(256), 0, stream, n);
+        AAE_CB_LAUNCH((aae::l2norm_pack_bf16x3_kernel), dim3(ceil_div(s.Bpad, 4)), dim3(256), 0, stream, n);
         AAE_HIP_TRY(hipGetLastError());
         if (resident) return launch_scan_resident(cb, n.qp3, B, s, base, stream, topk, nullptr, rfin);
         aae::ScanBf16Args a;
@@ -249,10 +305,10 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
         a.N = cb->N; a.B = B; a.Bpad = s.Bpad; a.Bstride = s.Bstride; a.col_stride = col_stride;
         if (col_stride > 1) {
             (void)hipFuncSetAttribute((const void*)aae::scan_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kScanBf16Smem);
-            AAE_LAUNCH((aae::scan_bf16_kernel<true>), dim3(s.nblk), dim3(256), aae::kScanBf16Smem, stream, a);
+            AAE_CB_LAUNCH((aae::scan_bf16_kernel<true>), dim3(s.nblk), dim3(256), aae::kScanBf16Smem, stream, a);
         } else {
             (void)hipFuncSetAttribute((const void*)aae::scan_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kScanBf16Smem);
-            AAE_LAUNCH((aae::scan_bf16_kernel<false>), dim3(s.nblk), dim3(256), aae::kScanBf16Smem, stream, a);
+            AAE_CB_LAUNCH((aae::scan_bf16_kernel<false>), dim3(s.nblk), dim3(256), aae::kScanBf16Smem, stream, a);
         }
         AAE_HIP_TRY(hipGetLastError());
         return AAE_OK;
@@ -261,7 +317,7 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
         aae::L2NormArgs n;
         n.z = z; n.q = q; n.qp = s.gemv ? nullptr : qp; n.B = B; n.J = cb->J; n.Jpad = s.Jpad; n.Bpad = s.gemv ? B : s.Bpad;
         if (resident && topk > 1 && cb->topk_prune) n.prune = reinterpret_cast<int*>(base + s.prune_off);
-        AAE_LAUNCH((aae::l2norm_pack_kernel), dim3(ceil_div(n.Bpad, 4)), dim3(256), 0, stream, n);
+        AAE_CB_LAUNCH((aae::l2norm_pack_kernel), dim3(ceil_div(n.Bpad, 4)), dim3(256), 0, stream, n);
         AAE_HIP_TRY(hipGetLastError());
     }
     if (resident) return launch_scan_resident(cb, qp, B, s, base, stream, topk, nullptr, rfin);
@@ -290,7 +346,14 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
         else launch_scan_walk_t<4>(a, upright, blocks, stream);
     } else
 #endif
-    if (s.stream) {
+    if (s.topk_stream && topk > 1 && fin) {                 // sorted lists per block instead of the arg-max partials
+        scan_topk_args(a, s, base, topk, *fin);
+        if (B == 1) launch_scan_stream_k<1>(a, s.nblk, stream);
+        else if (B == 2) launch_scan_stream_k<2>(a, s.nblk, stream);
+        else if (B == 3) launch_scan_stream_k<3>(a, s.nblk, stream);
+        else launch_scan_stream_k<4>(a, s.nblk, stream);
+        if (!a.tickets) launch_scan_topk_merge_lists(a, s.nblk, stream);
+    } else if (s.stream) {
         if (B == 1) launch_scan_stream_t<1>(a, upright, s.nblk, stream);
         else if (B == 2) launch_scan_stream_t<2>(a, upright, s.nblk, stream);
         else if (B == 3) launch_scan_stream_t<3>(a, upright, s.nblk, stream);
@@ -299,8 +362,8 @@ static int run_scan(aae_codebook* cb, const float* z, int B, int col_stride, flo
 #ifdef AAE_EXPERIMENTS
     else if (s.gemv) {
         const int smem = 2 * 4 * 4 * (int)sizeof(float);
-        if (upright) AAE_LAUNCH((aae::scan_gemv_kernel<4, true>), dim3(s.nblk), dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::scan_gemv_kernel<4, false>), dim3(s.nblk), dim3(256), smem, stream, a);
+        if (upright) AAE_CB_LAUNCH((aae::scan_gemv_kernel<4, true>), dim3(s.nblk), dim3(256), smem, stream, a);
+        else AAE_CB_LAUNCH((aae::scan_gemv_kernel<4, false>), dim3(s.nblk), dim3(256), smem, stream, a);
     }
 #endif
     else if (s.NT == 1) launch_scan_mfma_t<1>(a, upright, s.nblk, stream);

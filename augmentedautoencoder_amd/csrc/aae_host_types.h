@@ -209,4 +209,7 @@ struct aae_codebook {
     int scan_fused_norm = 1;
     int scan_resident_fin = 0;   // AAE_SCAN_AUTO_FIN: the B <= 32 resident scan answers inside its launch (ticket finish) instead of an argmax_reduce launch
     int scan_rh4 = 1;      // B <= 32, top-1 on the query-resident kernel: rows of a tile over four waves per query group (AAE_SCAN_AUTO_RH2: 0 = two, A/B)
+    // B <= 4, top-k 2 ... 8 on a stream kernel: 1 = sorted lists per block inside the scan, merged by the last block to arrive (one launch);
+    // 0 (AAE_SCAN_AUTO_TOPK_ROWS) = the scan writes the [B][N] similarity rows, topk_chunks_kernel + topk_merge_kernel select -- identical bits
+    int scan_topk_stream = 1;
 };

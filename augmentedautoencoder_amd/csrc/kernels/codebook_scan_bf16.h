@@ -160,7 +160,8 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const ScanBf16Args p) {
 // fp32-normalised queries (no query splitting needed off the matrix cores); row16_reduce_scatter16 sums the 16 rows of a
 // group over its 16 lanes in 45 cross-lane instructions (16 separate four-step trees: 64) and leaves row l of the wave's
 // 64 in lane l; the block's scores meet in LDS and wave b finds (max, first row) of query b (scan_block_argmax_store).
-template <int NQ, bool UPRIGHT, bool WITH_CS>
+// K > 0: top-k lists per block instead of the arg-max partial (scan_block_topk_store, codebook_scan_f32.h).
+template <int NQ, bool UPRIGHT, bool WITH_CS, int K = 0>
 __global__ __launch_bounds__(256) void scan_stream_bf16_kernel(const ScanArgs p) {
     AAE_DYN_SMEM(smem_raw);
     float* sc = reinterpret_cast<float*>(smem_raw);              // [NQ][256] scores of the block's rows
@@ -233,8 +234,13 @@ __global__ __launch_bounds__(256) void scan_stream_bf16_kernel(const ScanArgs p)
         sc[b * 256 + wave * 64 + lane] = cand ? dot : kNegInf;
     }
     __syncthreads();
-    scan_block_argmax_store<NQ, 256>(p, sc, blockIdx.x * 256, blockIdx.x, gridDim.x);   // wave b: (max, first row) of query b over the block's 256 rows
-    if (p.tickets) scan_ticket_finish<NQ>(p, sc + NQ * 256, blockIdx.x, gridDim.x);
+    if constexpr (K > 0) {
+        scan_block_topk_store<NQ, K, 256>(p, sc, blockIdx.x * 256, blockIdx.x, gridDim.x);
+        if (p.tickets) scan_ticket_finish_topk<NQ, K>(p, sc + NQ * 256, sc, blockIdx.x, gridDim.x);
+    } else {
+        scan_block_argmax_store<NQ, 256>(p, sc, blockIdx.x * 256, blockIdx.x, gridDim.x);   // wave b: (max, first row) of query b over the block's 256 rows
+        if (p.tickets) scan_ticket_finish<NQ>(p, sc + NQ * 256, blockIdx.x, gridDim.x);
+    }
 }
 
 }  // namespace aae

@@ -76,6 +76,10 @@ struct ScanArgs {
     long long* idx_out = nullptr;   // [B] int64
     float* score_out = nullptr;     // [B]
     int idx_scale = 1;              // row ids are multiplied by this (upright search on the compacted copy)
+    // stream kernels, top-k (k = 2 ... 8, scan_block_topk_store): every block leaves a sorted list per query here instead of a
+    // similarity row; idx_out / score_out are then [B][k]
+    float* cand = nullptr;          // [blocks][B][scan_list_entries(K)] (score, row) pairs
+    int k = 0;
 };
 
 // block-wide (value, index) arg-best in np.argmax order; result broadcast to every thread.  red: 10 dwords of LDS.
@@ -281,8 +285,175 @@ __device__ __forceinline__ void scan_block_argmax_store(const ScanArgs& p, const
     }
 }
 
+// ---- top-k (k = 2 ... 8) inside the stream scans (codebook.py:69-71 for the reference's one-crop-per-call usage) -------------
+// The block keeps no similarity row.  After its scores meet in LDS wave b extracts the K best (score, row) of query b over the
+// block's rows -- K rounds of wave_max_first_position, the winner's slot set to -inf: positions ascend like rows, so the order
+// is that of better() (higher score first, lower row first among equals) -- and lane 0 stores the list as 16-byte
+// device-coherent pieces of two entries, [block][query][entry]; unused entries are (-inf, 0x7fffffff).  K: list slots, the
+// smallest instantiated value >= k (2, 4, 5, 8: launch_scan_resident_k's set); an odd K is padded to whole pieces.
+constexpr int scan_list_entries(int K) { return (K + 1) & ~1; }
+
+template <int NQ, int K, int ROWS>
+__device__ __forceinline__ void scan_block_topk_store(const ScanArgs& p, const float* sc, int row_base, const unsigned blk, const unsigned nblk) {
+    const int lane = threadIdx.x & 63, wave = wave_uniform(threadIdx.x >> 6);
+    if (wave >= NQ || wave >= p.B) return;                       // wave-uniform
+    constexpr int NV = ROWS / 64, KE = scan_list_entries(K);
+    float v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = sc[wave * ROWS + 64 * j + lane];
+    uint32_t ls[KE], lr[KE];
+#pragma unroll
+    for (int r = 0; r < KE; ++r) {
+        ls[r] = __builtin_bit_cast(uint32_t, kNegInf);
+        lr[r] = 0x7fffffffu;
+        if (r < K) {
+            int first;
+            const float m = wave_max_first_position<NV>(v, first);
+            if (m > kNegInf) { ls[r] = __builtin_bit_cast(uint32_t, m); lr[r] = (uint32_t)(row_base + first); }
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (first == 64 * j + lane) v[j] = kNegInf;
+        }
+    }
+    if (lane != 0) return;
+    const buffer_rsrc cbuf = make_buffer(p.cand, nblk * (unsigned)p.B * (unsigned)(KE * 8));
+#pragma unroll
+    for (int h = 0; h < KE / 2; ++h) {
+        u32x4 piece;
+        piece[0] = ls[2 * h]; piece[1] = lr[2 * h]; piece[2] = ls[2 * h + 1]; piece[3] = lr[2 * h + 1];
+        coherent_store4(cbuf, ((blk * (unsigned)p.B + (unsigned)wave) * KE + 2u * h) * 8u, __builtin_bit_cast(f32x4, piece));
+    }
+}
+
+// Same-wave LDS traffic is ordered on the device.  Under the fiber emulator (tests/emu/) the lanes of a wave are fibers that
+// meet only in the wave collectives: one of those between a lane's LDS write and another lane's read of it.
+__device__ __forceinline__ void wave_lds_handover() { (void)wave_any(true); }
+
+// The k best of query q = wave over the `nblk` block lists: an exact k-way merge, one wave per query, no block barrier.
+//   * Lane l holds lists kScanListSlots l ... + kScanListSlots - 1 of a chunk of 64 kScanListSlots lists (768: the default
+//     codebook's 721 blocks are one chunk) -- blocks, and with them rows, ascend with (lane, slot), so "first slot of the lane,
+//     then wave_max_first_lane" resolves equal scores to the lowest row, as better() does.  The first piece of every list (its
+//     two best entries) is requested before any is looked at.
+//   * Round r pops the best head of the wave: the owner lane writes (score, row) to result slot r and its list moves on to its
+//     next entry.  The lists are sorted, so no other entry of any list can be the next winner: a list is read beyond its first
+//     piece only once BOTH entries of that piece are among the winners (at most k / 2 lists, usually none or one) -- one
+//     8-byte device-coherent load by the owner lane then.
+//   * More than one chunk: the winners so far are one more sorted list (they come from lower blocks: they win equal scores).
+// Every decision depends on the lists' contents alone, never on which block arrived when.
+// lds: 4 K dwords per query (two result lists of K (score, row) pairs, written in turn).
+constexpr int kScanListSlots = 12;
+template <int K>
+__device__ __forceinline__ void scan_topk_merge_lists(const ScanArgs& p, uint32_t* lds, const int nblk) {
+    const int lane = threadIdx.x & 63, q = wave_uniform(threadIdx.x >> 6);
+    if (q >= p.B) return;                                         // wave-uniform
+    constexpr int KE = scan_list_entries(K), LP = kScanListSlots;
+    const buffer_rsrc cbuf = make_buffer(p.cand, (unsigned)nblk * (unsigned)p.B * (unsigned)(KE * 8));
+    uint32_t* res = lds + q * 4 * K;                              // [2][K][2]
+    int cur = 0;                                                  // the result list this chunk writes
+    for (int c0 = 0; c0 < nblk; c0 += 64 * LP) {                  // wave-uniform
+        const uint32_t* prev = res + (cur ^ 1) * 2 * K;
+        uint32_t* out = res + cur * 2 * K;
+        f32x4 t[LP];
+#pragma unroll
+        for (int j = 0; j < LP; ++j) {
+            const int blk = c0 + lane * LP + j;
+            t[j] = coherent_load4(cbuf, blk < nblk ? (unsigned)((blk * p.B + q) * KE) * 8u : kOobOffset);
+        }
+        float hs[LP], ns[LP];                                     // head of list j, the entry behind it (while depth 0)
+        int hr[LP], nr[LP], dep[LP];                              // ... their rows; entries popped so far
+#pragma unroll
+        for (int j = 0; j < LP; ++j) {
+            const bool live = c0 + lane * LP + j < nblk;
+            const u32x4 piece = __builtin_bit_cast(u32x4, t[j]);  // (whole vector, then scalars: see device_intrinsics.h)
+            const uint32_t w0 = piece[0], w1 = piece[1], w2 = piece[2], w3 = piece[3];
+            hs[j] = live ? __builtin_bit_cast(float, w0) : kNegInf;
+            hr[j] = live ? (int)w1 : 0x7fffffff;
+            ns[j] = live ? __builtin_bit_cast(float, w2) : kNegInf;
+            nr[j] = live ? (int)w3 : 0x7fffffff;
+            dep[j] = 0;
+        }
+        float cvs[K];                                             // scores of the winners of the chunks before (wave-uniform)
+        int cd = K;                                               // ... consumed so far (first chunk: there are none)
+        if (c0 > 0) {
+            cd = 0;
+#pragma unroll
+            for (int i = 0; i < K; ++i) cvs[i] = __builtin_bit_cast(float, prev[2 * i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < K; ++i) cvs[i] = kNegInf;
+        }
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            if (r < p.k) {                                        // wave-uniform
+                float bs = hs[0];
+                int bj = 0;
+#pragma unroll
+                for (int j = 1; j < LP; ++j)
+                    if (hs[j] > bs) { bs = hs[j]; bj = j; }
+                int fl;
+                const float m = wave_max_first_lane(bs, fl);
+                float chead = kNegInf;
+#pragma unroll
+                for (int i = 0; i < K; ++i)
+                    if (i == cd) chead = cvs[i];
+                if (cd < K && chead >= m) {                        // wave-uniform
+                    if (lane == 0) { out[2 * r] = prev[2 * cd]; out[2 * r + 1] = prev[2 * cd + 1]; }
+                    ++cd;
+                } else {
+                    const bool own = lane == fl;
+                    uint32_t es = 0u, er = 0u;
+                    int d = 0;
+#pragma unroll
+                    for (int j = 0; j < LP; ++j)
+                        if (own && j == bj) { es = __builtin_bit_cast(uint32_t, hs[j]); er = (uint32_t)hr[j]; d = ++dep[j]; }
+                    if (own) { out[2 * r] = es; out[2 * r + 1] = er; }
+                    const int blk = c0 + lane * LP + bj;
+                    const bool need = own && d >= 2 && d < K && blk < nblk;
+                    float s2 = kNegInf;
+                    int r2 = 0x7fffffff;
+                    if (wave_any(need)) {                          // both entries of a first piece have won: the list's entry d
+                        const unsigned off = need ? (unsigned)((blk * p.B + q) * KE + d) * 8u : kOobOffset;
+                        const uint32_t a0 = coherent_load1(cbuf, off), a1 = coherent_load1(cbuf, off + 4u);
+                        if (need) { s2 = __builtin_bit_cast(float, a0); r2 = (int)a1; }
+                    }
+#pragma unroll
+                    for (int j = 0; j < LP; ++j)
+                        if (own && j == bj) {
+                            hs[j] = d == 1 ? ns[j] : s2;
+                            hr[j] = d == 1 ? nr[j] : r2;
+                        }
+                }
+            }
+        }
+        wave_lds_handover();
+        cur ^= 1;
+    }
+    const uint32_t* fin = res + (cur ^ 1) * 2 * K;
+    if (lane < p.k) {
+        const uint32_t s = fin[2 * lane], r = fin[2 * lane + 1];
+        p.idx_out[(long long)q * p.k + lane] = r == 0x7fffffffu ? 0ll : (long long)r * p.idx_scale;   // (fewer than k scores that are numbers: topk_merge_kernel answers 0 too)
+        p.score_out[(long long)q * p.k + lane] = __builtin_bit_cast(float, s);
+    }
+}
+
+// ... by the last block of the scan to arrive (cf. scan_ticket_finish; lds: the block's score rows, free behind the barrier of
+// block_ticket_arrive: >= 4 K dwords per query)
+template <int NQ, int K>
+__device__ __forceinline__ void scan_ticket_finish_topk(const ScanArgs& p, float* red, float* lds, const unsigned blk, const unsigned nblk_u) {
+    int* flag = reinterpret_cast<int*>(red) + 10;
+    if (!block_ticket_arrive(p.tickets, p.nonce, nblk_u, blk, flag)) return;
+    scan_topk_merge_lists<K>(p, reinterpret_cast<uint32_t*>(lds), (int)nblk_u);
+}
+// ... or by a launch of its own behind the scan (AAE_SCAN_STREAM_2L: no in-launch finish): one block, wave q answers query q
+template <int K>
+__global__ __launch_bounds__(256) void scan_topk_merge_lists_kernel(const ScanArgs p, const int nblk) {
+    AAE_DYN_SMEM(smem_raw);
+    scan_topk_merge_lists<K>(p, reinterpret_cast<uint32_t*>(smem_raw), nblk);
+}
+
 // block `blk` of the `nblk` blocks that scan this codebook (sm: NQ * 128 floats of scores + kScanTicketSmem bytes)
-template <int NQ, bool UPRIGHT, bool WITH_CS>
+// K > 0: top-k lists instead of the arg-max partial (no similarity row, no masked candidates)
+template <int NQ, bool UPRIGHT, bool WITH_CS, int K = 0>
 __device__ __forceinline__ void scan_stream_block(const ScanArgs& p, const int blk, const int nblk, unsigned char* smem_raw) {
     float* sc = reinterpret_cast<float*>(smem_raw);              // [NQ][128] scores of the block's rows
 
@@ -318,14 +489,19 @@ __device__ __forceinline__ void scan_stream_block(const ScanArgs& p, const int b
         if (!(lane & 1)) sc[b * 128 + wave * 32 + (lane >> 1)] = cand ? d : kNegInf;
     }
     __syncthreads();
-    scan_block_argmax_store<NQ, 128>(p, sc, blk * 128, (unsigned)blk, (unsigned)nblk);
-    if (p.tickets) scan_ticket_finish<NQ>(p, sc + NQ * 128, (unsigned)blk, (unsigned)nblk);
+    if constexpr (K > 0) {
+        scan_block_topk_store<NQ, K, 128>(p, sc, blk * 128, (unsigned)blk, (unsigned)nblk);
+        if (p.tickets) scan_ticket_finish_topk<NQ, K>(p, sc + NQ * 128, sc, (unsigned)blk, (unsigned)nblk);
+    } else {
+        scan_block_argmax_store<NQ, 128>(p, sc, blk * 128, (unsigned)blk, (unsigned)nblk);
+        if (p.tickets) scan_ticket_finish<NQ>(p, sc + NQ * 128, (unsigned)blk, (unsigned)nblk);
+    }
 }
 
-template <int NQ, bool UPRIGHT, bool WITH_CS>
+template <int NQ, bool UPRIGHT, bool WITH_CS, int K = 0>
 __global__ __launch_bounds__(256) void scan_stream_kernel(const ScanArgs p) {
     AAE_DYN_SMEM(smem_raw);
-    scan_stream_block<NQ, UPRIGHT, WITH_CS>(p, (int)blockIdx.x, (int)gridDim.x, smem_raw);
+    scan_stream_block<NQ, UPRIGHT, WITH_CS, K>(p, (int)blockIdx.x, (int)gridDim.x, smem_raw);
 }
 
 // ---- SEVERAL codebooks in one launch (multi_launch.h): blocks [first[o], first[o + 1]) stream codebook o against object o's

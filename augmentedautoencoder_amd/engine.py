@@ -355,48 +355,59 @@ class EncoderEngine(object):
                 torch.cuda.current_stream().synchronize()
             self._x3h_note(redo)
 
-    def encode_nn(self, codebook_engine, x, col_stride=1, out=None):
-        """Encoder.z + the top-1 codebook query of a batch in one C call per chunk (aae_encode_nn): what
-        Codebook.nearest_rotation does per detection.  Returns (z [B,J], idx int64 [B,1], cosine float32 [B,1]) on
-        the device; bit-identical to encode() followed by codebook_engine.nn(z, 1, col_stride).  out: optional
+    def encode_nn(self, codebook_engine, x, col_stride=1, out=None, topk=1):
+        """Encoder.z + the codebook query of a batch in one C call per chunk (aae_encode_nn; topk > 1: aae_encode_nn_topk): what
+        Codebook.nearest_rotation does per detection.  Returns (z [B,J], idx int64 [B,topk], cosine float32 [B,topk]) on
+        the device; bit-identical to encode() followed by codebook_engine.nn(z, topk, col_stride).  out: optional
         caller-owned (z, idx, score) device tensors of at least B rows to write into (a per-frame loop then allocates nothing)."""
         torch = _torch()
         cb = codebook_engine
+        topk = int(topk)
+        if topk < 1:
+            raise ValueError('encode_nn: topk %d < 1' % topk)
+        if topk > 1 and int(col_stride) != 1:
+            raise ValueError('encode_nn: upright (col_stride > 1) is defined for topk == 1 only')
         if cb.device != self.device:
             raise ValueError('encode_nn: encoder on %s, codebook on %s -- one C call needs both on one device' % (self.device, cb.device))
         t = self.to_device_batch(x)
         B = t.shape[0]
         if out is not None:
             z, idx, score = out[0][:B], out[1][:B], out[2][:B]
-            if (z.shape != (B, self.cfg.latent_space_size) or idx.shape != (B, 1) or score.shape != (B, 1) or z.dtype != torch.float32
+            if (z.shape != (B, self.cfg.latent_space_size) or idx.shape != (B, topk) or score.shape != (B, topk) or z.dtype != torch.float32
                     or idx.dtype != torch.int64 or score.dtype != torch.float32 or not (z.is_contiguous() and idx.is_contiguous() and score.is_contiguous())
                     or z.device != self.device or idx.device != self.device or score.device != self.device):
-                raise ValueError('encode_nn(out=...): need contiguous float32 [>=B,J], int64 [>=B,1], float32 [>=B,1] tensors on %s' % (self.device,))
+                raise ValueError('encode_nn(out=...): need contiguous float32 [>=B,J], int64 [>=B,%d], float32 [>=B,%d] tensors on %s' % (topk, topk, self.device))
         else:
             z = torch.empty((B, self.cfg.latent_space_size), dtype=torch.float32, device=self.device)
-            idx = torch.empty((B, 1), dtype=torch.int64, device=self.device)
-            score = torch.empty((B, 1), dtype=torch.float32, device=self.device)
+            idx = torch.empty((B, topk), dtype=torch.int64, device=self.device)
+            score = torch.empty((B, topk), dtype=torch.float32, device=self.device)
         if B == 0:
             return z, idx, score
-        cb.ensure_upright(col_stride, 1)
+        cb.ensure_upright(col_stride, topk)
         dt = _lib.AAE_DTYPE_U8 if t.dtype == torch.uint8 else _lib.AAE_DTYPE_F32
         for a in range(0, B, self.max_batch):
             e = min(a + self.max_batch, B)
             n = e - a
             nb_e = self.workspace_bytes(n)
-            nb_c = cb.workspace_bytes(n, 1)
+            nb_c = cb.workspace_bytes(n, topk)
             _, ws_e = self.ws.get(nb_e)
             _, ws_c = cb.ws.get(nb_c)
             self._last_B = n
             with _on_device(self.device):
-                rc = self.lib.aae_encode_nn(self.handle, cb.handle, ctypes.c_void_p(t[a:e].data_ptr()), dt, n, int(col_stride),
-                                            ctypes.c_void_p(z[a:e].data_ptr()), ctypes.c_void_p(idx[a:e].data_ptr()),
-                                            ctypes.c_void_p(score[a:e].data_ptr()), ctypes.c_void_p(ws_e), nb_e,
-                                            ctypes.c_void_p(ws_c), nb_c, _stream_ptr(torch))
-            _lib.check(self.lib, rc, 'aae_encode_nn')
+                if topk == 1:
+                    rc = self.lib.aae_encode_nn(self.handle, cb.handle, ctypes.c_void_p(t[a:e].data_ptr()), dt, n, int(col_stride),
+                                                ctypes.c_void_p(z[a:e].data_ptr()), ctypes.c_void_p(idx[a:e].data_ptr()),
+                                                ctypes.c_void_p(score[a:e].data_ptr()), ctypes.c_void_p(ws_e), nb_e,
+                                                ctypes.c_void_p(ws_c), nb_c, _stream_ptr(torch))
+                else:
+                    rc = self.lib.aae_encode_nn_topk(self.handle, cb.handle, ctypes.c_void_p(t[a:e].data_ptr()), dt, n, topk,
+                                                     ctypes.c_void_p(z[a:e].data_ptr()), ctypes.c_void_p(idx[a:e].data_ptr()),
+                                                     ctypes.c_void_p(score[a:e].data_ptr()), ctypes.c_void_p(ws_e), nb_e,
+                                                     ctypes.c_void_p(ws_c), nb_c, _stream_ptr(torch))
+            _lib.check(self.lib, rc, 'aae_encode_nn' if topk == 1 else 'aae_encode_nn_topk')
 
             def redo(a=a, e=e):
-                za, ia, sa = self.encode_nn(cb, t[a:e], col_stride)
+                za, ia, sa = self.encode_nn(cb, t[a:e], col_stride, topk=topk)
                 z[a:e], idx[a:e], score[a:e] = za, ia, sa
             self._x3h_note(redo)
         return z, idx, score

@@ -42,8 +42,8 @@ extern "C" {
 
 #define AAE_MAX_LAYERS 8
 
-#define AAE_SCAN_AUTO 0           /* B <= 4: streaming kernel that answers inside its launch; B > 4, top-1 / top-2..8, stride 1:
-                                    * query-resident MFMA kernel; else the tile-resident MFMA kernels                        */
+#define AAE_SCAN_AUTO 0           /* B <= 4, top-1 / top-2..8: streaming kernel that answers inside its launch; B > 4, top-1 /
+                                    * top-2..8, stride 1: query-resident MFMA kernel; else the tile-resident MFMA kernels    */
 #define AAE_SCAN_AUTO_PACKED 7    /* AUTO, but the top-1 query-resident scan (B > 4) reads queries normalised and packed by a
                                      launch in front instead of normalising the raw codes in its own prologue: A/B, same answers
                                      (the other A/B modes: include/aae_hip_tuning.h) */
@@ -176,11 +176,18 @@ size_t aae_codebook_workspace_bytes(const aae_codebook* cb, int B, int topk);
  * top-n (:69-71).  col_stride = 1, or num_cyclo for `upright` (:66; only with topk 1).
  * idx_out: device int64 [B, topk]; score_out: device float32 [B, topk] (cosine).
  * Ties resolve to the lowest index (np.argmax); top-k is score-descending,
- * index-ascending among equal scores.  topk 2..8 with B > 4 is computed inside the scan
- * (sorted per-lane lists); other top-k requests materialise the [B,N] similarity in the
- * workspace first -- aae_codebook_workspace_bytes(cb, B, topk) accounts for either. */
+ * index-ascending among equal scores.  topk 2..8 is computed inside the scan: B <= 4 (the
+ * reference's one-crop-per-call top-n) in ONE launch -- every block of the streaming kernel
+ * leaves a sorted list per query and the last block to arrive merges them; B > 4 on the
+ * query-resident kernel (sorted per-lane lists) + a merge launch.  topk > 8 materialises the
+ * [B,N] similarity in the workspace first -- aae_codebook_workspace_bytes(cb, B, topk)
+ * accounts for either. */
 int aae_codebook_nn(aae_codebook* cb, const float* z, int B, int topk, int col_stride,
                     int64_t* idx_out, float* score_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* Kernel launches the calling thread's last aae_codebook_nn call queued; after aae_encode_nn / aae_encode_nn_topk: the launches
+ * of that call's codebook stage.  Thread-local, like aae_multi_last_launches. */
+int aae_codebook_last_launches(void);
 
 /* The same query `reps` times back to back, queued from C between two HIP events on `stream`: *period_ms = device time per
  * query = its kernel(s) + the dependent-launch gap, without the caller's per-call host cost (a Python loop spends longer per
@@ -199,6 +206,15 @@ int aae_codebook_nn_timed(aae_codebook* cb, const float* z, int B, int topk, int
 int aae_encode_nn(aae_encoder* enc, aae_codebook* cb, const void* x, int x_dtype, int B, int col_stride, float* z_out,
                   int64_t* idx_out, float* score_out, void* enc_workspace, size_t enc_ws_bytes, void* cb_workspace,
                   size_t cb_ws_bytes, void* stream);
+
+/* aae_encode_nn with a top-k scan (col_stride 1): aae_encoder_forward followed by aae_codebook_nn(topk) in ONE call -- what
+ * Codebook.nearest_rotation(session, x, top_n) does for its single crop (auto_pose/ae/codebook.py:55-71, eval/ae_eval.py:173-201).
+ * Same results as the two calls, bit for bit.  B <= 4, topk 2..8: still six launches, the scan's ticket words prepared by the
+ * encoder's first kernel; otherwise the two calls back to back.  idx_out / score_out: device [B, topk].
+ * cb_workspace: aae_codebook_workspace_bytes(cb, B, topk). */
+int aae_encode_nn_topk(aae_encoder* enc, aae_codebook* cb, const void* x, int x_dtype, int B, int topk, float* z_out,
+                       int64_t* idx_out, float* score_out, void* enc_workspace, size_t enc_ws_bytes, void* cb_workspace,
+                       size_t cb_ws_bytes, void* stream);
 
 /* Full cosine-similarity matrix cs_out [B,N] (device) = session.run(cos_similarity)
  * (codebook.py:63); parity / debugging path, the nn call never materialises it for topk 1. */

@@ -33,6 +33,9 @@
 #define AAE_SCAN_AUTO_RH2 8       /* AUTO, but <= 32 queries split a tile's rows over two waves per query group instead of four      */
 #define AAE_SCAN_AUTO_FIN 9       /* AUTO, and the <= 32-query resident scan answers inside its launch (ticket finish): measured
                                      slower than the reduce launch it replaces (20.7 vs 16.1 us), opt-in                             */
+#define AAE_SCAN_AUTO_TOPK_ROWS 10 /* AUTO, but top-k 2..8 of B <= 4 queries the earlier way: the stream scan writes the [B,N] similarity
+                                     rows, a chunk-selection and a merge launch follow (three launches; A/B partner and bitwise
+                                     reference of the in-scan lists)                                                                 */
 
 /* ---- encoder options (aae_encoder_set_option(enc, name, value)); defaults in parentheses ---------------------------------------
  * large batches (128-row implicit GEMM, conv_igemm_f32.h / conv_igemm_x3h.h)
