@@ -116,10 +116,10 @@ int aae_encoder_create(const aae_encoder_desc* d, const void* const* hw, int n_w
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<0>());
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<0>());
     (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<2, 2, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<0>());
-    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 3, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<1>());
-    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<1>());
-    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<1>());
-    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<2, 2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<1>());
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 3, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<2>());
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<2>());
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<3, 2, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<2>());
+    (void)hipFuncSetAttribute((const void*)aae::conv_wino_phase_kernel<2, 2, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_smem_bytes<2>());
 #endif
     (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
     (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<false, true, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
@@ -305,6 +305,8 @@ int aae_encoder_set_option(aae_encoder* enc, const char* name, int value) {
         enc->winograd_wide = value ? 1 : 0;
     } else if (!strcmp(name, "winograd_stage32")) {
         enc->winograd_stage32 = value ? 1 : 0;
+    } else if (!strcmp(name, "winograd_static_halo")) {
+        enc->winograd_static_halo = value ? 1 : 0;
     } else if (!strcmp(name, "winograd_min_batch")) {
         enc->winograd_min_batch = value < 1 ? 1 : value;
     } else if (!strcmp(name, "winograd_min_fill_pct")) {

@@ -575,7 +575,7 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
             a.eh = eh; a.ew = ew; a.U = L.wino[2 * eh + ew];
             a.mode = i == 0 ? 0 : (i == 3 ? 2 : 1);
             if (L.wino_geom == 0) launch_wino_phase<0>(a, eh, ew, grid, stream);
-            else launch_wino_phase<1>(a, eh, ew, grid, stream);
+            else launch_wino_phase<2>(a, eh, ew, grid, stream);      // (four windows of their own: WinoGeom<2>)
             const int taps = (eh ? 3 : 2) * (ew ? 3 : 2), points = ((eh ? 3 : 2) + 1) * ((ew ? 3 : 2) + 1);
             snprintf(label, sizeof(label), "%s:conv_wino_f32 phase %d%d (%d taps as %d products per 2x2 outputs) M=%d N=%d C=%d", name, eh, ew, taps, points,
                      B * L.Ho * L.Wo, L.Cout, L.Cin);
@@ -590,7 +590,7 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
     aae::ConvWinoLayerArgs p;
     p.c = a;
     for (int i = 0; i < 4; ++i) p.U4[i] = L.wino[i];
-    wino_layer_launch(L.wino_geom, enc->winograd_wide, enc->winograd_stage32, grid, stream, p);
+    wino_layer_launch(L.wino_geom, enc->winograd_wide, enc->winograd_stage32, grid, stream, p, enc->winograd_static_halo);
     // (the record carries the flops the kernel EXECUTES -- 49 products per 2 x 2 outputs and channel pair where the direct form
     //  multiplies 100 -- so that its TFLOP/s figure is a statement about the kernel)
     snprintf(label, sizeof(label), "%s:conv_wino_f32 layer (25 taps as 49 products per 2x2 outputs) M=%d N=%d C=%d", name, B * L.Ho * L.Wo, L.Cout, L.Cin);

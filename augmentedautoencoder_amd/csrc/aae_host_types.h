@@ -109,6 +109,7 @@ struct aae_encoder {
     int multi_mid_ragged = 1;              // ... and a layer of four-image blocks (8 x 8 outputs) hands the objects' LAST 1-3 images to one grouped wave-split-K launch when the ragged
                                            // blocks would open one more round of blocks (config 4: 67 groups = 536 blocks = 3 rounds -> 61 groups + 12 images); 0 = ragged blocks
     int winograd_stage32 = 1;              // 32-channel LDS stages in the Winograd layer kernel where they fit (16 x 16-pixel regions, 32 | Cin); 0 = 16-channel stages: the same bits
+    int winograd_static_halo = 1;          // the zero halo of a block's window written once per block where the block covers whole sub-images (conv3, conv4); 0 = loaded in every stage: the same bits
     int winograd_xcd_cols = -1;            // column blocks of a region that share an XCD (aae_encoder_launch.h: wino_xcd_cols); -1 = per-layer default
     int first_target_blocks = 512;         // conv1 grid size aimed at (x N tiles); 2 blocks fit a CU
     int first_group_split_max_tiles = 128; // conv1: batches of at most this many 128-pixel tiles (B <= 4 of the default net) run one block per 32-pixel group

@@ -647,7 +647,7 @@ static int launch_encoder_multi(const aae_multi_item* items, const MultiPlan& mp
             wm.range.first[members.size()] = wat;
             c.regions = wat;
             c.xcd_cols = wino_xcd_cols(enc0, L0);
-            wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(wat, L0.Cout / 64, c.xcd_cols), stream, wm);
+            wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(wat, L0.Cout / 64, c.xcd_cols), stream, wm, enc0->winograd_static_halo);
             AAE_HIP_TRY(hipGetLastError());
             ++t_multi_launches;
             continue;
@@ -815,7 +815,7 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
         m.range.first[members.size()] = at;
         c.regions = at;
         c.xcd_cols = wino_xcd_cols(enc0, L0);
-        wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(at, L0.Cout / 64, c.xcd_cols), stream, m);
+        wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(at, L0.Cout / 64, c.xcd_cols), stream, m, enc0->winograd_static_halo);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
         if (split) {

@@ -19,13 +19,14 @@
 // output is written once with bias / ReLU / BN).  The experiments build also has one launch per PHASE (the phases add up in the output
 // buffer: measured 2 % slower, tools/wino_ab.py).  Either way:
 //   block = 8 waves = 64 tiles x 64 output channels.  GEOM 0: an 8 x 8-tile (16 x 16-pixel) region of one image (conv2, conv3);
-//           GEOM 1: the 4 x 4 tiles of four images (conv4: 8 x 8 outputs).  Wave (mh, nh, ph): 32 tiles x 32 channels x HALF the points --
+//           GEOM 1: the 4 x 4 tiles of four images (conv4: 8 x 8 outputs; GEOM 2: the same blocks on the stage-buffer layout of the loading fill).  Wave (mh, nh, ph): 32 tiles x 32 channels x HALF the points --
 //           the point rows of the split dimension A go to two waves (rows {0, 1} | the rest), so a wave keeps 8 (6, 3) accumulator tiles
 //           = at most 128 registers, two waves share a SIMD and one's cluster (patch reads, transform, loads) runs under the other's
 //           MFMA burst.  The two halves of the output transform meet through LDS once per phase.  A = rows, or columns when SWAP (the
 //           2 x 3-tap phase: the 3-tap dimension is the one that splits evenly).
-//   K loop = stages of 32 input channels (16 for GEOM 1 in the one-launch-per-layer kernel, whose exchange buffer leaves no room for more): the block's window of the sub-image (tiles + halo, zero outside the image = the 'SAME'
-//           padding) goes global -> registers -> LDS, double buffered, laid out [channel quad][image][column parity][row][column / 2]
+//   K loop = stages of 32 input channels (16 where the layer has no whole ones, and for GEOM 2 in the one-launch-per-layer kernel, whose exchange buffer leaves no
+//           room for more): the block's window of the sub-image (tiles + halo, zero outside the image = the 'SAME' padding; where the block covers the whole
+//           sub-image the halo is written ONCE per block and the fill moves the data only: WinoFillPlan) goes global -> registers -> LDS, double buffered, laid out [channel quad][image][column parity][row][column / 2]
 //           with pitches that make the patch reads (ds_read_b128 by 32 tiles) conflict-free.  The loop runs in units of one point row,
 //           each ONE cluster + ONE burst (wino_phase_body: the price list of what an instruction costs next to fp32 MFMAs): a lane transforms
 //           the patch rows it read before the previous burst with packed fp32 adds, loads the weight fragments of the unit after next (raw
@@ -86,21 +87,81 @@ struct WinoGeom<0> {         // one image, 8 x 8 tiles: window 18 x 18
     //   fill stores (ds_write_b128: groups of 8 consecutive lanes, conflict-free when their units differ mod 8): the lanes of a group are the
     //     8 channel quads of a pixel (planes 361 = 1 (mod 8) apart), or the 4 quads of two neighbouring pixels, which differ in their column
     //     parity (180 = 4 (mod 8) apart).
-    static constexpr int kImages = 1, kRows = 18, kCols = 18, kRowPitch = 10, kParityPitch = 180, kImagePitch = 2 * 180;
+    static constexpr int kImages = 1, kRows = 18, kCols = 18, kRowPitch = 10, kParityPitch = 180, kImagePitch = 2 * 180, kPlane = 2 * 180 + 1;
+    static constexpr int kFrameRows = 18, kFrameCols = 18;
+    __host__ __device__ static constexpr int image_offset(int) { return 0; }
+    __host__ __device__ static constexpr int frame_row(int) { return 0; }
+    __host__ __device__ static constexpr int frame_col(int) { return 0; }
 };
 template <>
-struct WinoGeom<1> {         // four images, 4 x 4 tiles each: windows 10 x 10
-    static constexpr int kImages = 4, kRows = 10, kCols = 10, kRowPitch = 6, kParityPitch = 60, kImagePitch = 128;
+struct WinoGeom<1> {         // four images, 4 x 4 tiles each: windows 10 x 10, laid out as ONE frame of 19 rows x 20 columns (a mosaic)
+    // Images (iy, ix) = (i >> 1, i & 1): two side by side with 10 frame columns each (an even offset: the column-parity split stays intact),
+    // two stacked with a SHARED zero row between them -- frame rows 0 | 1 ... 8 | 9 | 10 ... 17 | 18.  Row 9 is window row 9 of the upper
+    // image (source row 8) and window row 0 of the lower one (source row -1): outside the sub-image for both, in every stage of every
+    // component.  That is sound only with the static zero halo (WinoFillPlan<.., STATIC = true>: nobody refills the halo, so the shared row
+    // has no two owners); this geometry has no other fill.  Row pitch 10 (no spare unit), parity pitch 19 * 10 = 190, plane 381: 32-channel
+    // stages fit next to the layer kernel's exchange buffer (2 x 8 x 381 x 16 B + 64 KB = 159.25 KB of 160).  Bank conflicts
+    // (wino_geom_conflict_free below makes these compile-time facts):
+    //   patch reads: a tile's unit is 90 iy + 5 ix + 20 ty + tx + const = 10 iy + 5 ix + 4 ty + tx (mod 16), and wino_tile<1> gives every lane
+    //     group the 4 x 4 tiles of ONE image;
+    //   fill stores: the 8 channel quads of a pixel lie planes of 381 = 13 (mod 16) = 5 (mod 8) units apart.
+    static constexpr int kImages = 4, kRows = 10, kCols = 10, kRowPitch = 10, kParityPitch = 190, kPlane = 2 * 190 + 1;
+    static constexpr int kFrameRows = 19, kFrameCols = 20;
+    __host__ __device__ static constexpr int image_offset(int i) { return 90 * (i >> 1) + 5 * (i & 1); }
+    // frame position of window position (0, 0) of image i
+    __host__ __device__ static constexpr int frame_row(int i) { return 9 * (i >> 1); }
+    __host__ __device__ static constexpr int frame_col(int i) { return 10 * (i & 1); }
+};
+template <>
+struct WinoGeom<2> {         // four images, 4 x 4 tiles each, every 10 x 10 window a frame of its own (image pitch 128): the fill that loads the halo in
+    // every stage (option "winograd_static_halo" = 0), the 4-wave blocks and the one-launch-per-phase kernel of the experiments build; too
+    // large for 32-channel stages beside the exchange buffer
+    static constexpr int kImages = 4, kRows = 10, kCols = 10, kRowPitch = 6, kParityPitch = 60, kImagePitch = 128, kPlane = 4 * 128 + 1;
+    static constexpr int kFrameRows = 10, kFrameCols = 10;
+    __host__ __device__ static constexpr int image_offset(int i) { return i * kImagePitch; }
 };
 template <int GEOM>
-constexpr int wino_plane_units() { return WinoGeom<GEOM>::kImages * WinoGeom<GEOM>::kImagePitch + 1; }
+constexpr int wino_plane_units() { return WinoGeom<GEOM>::kPlane; }
 template <int GEOM>
 constexpr int wino_stage_units() { return 8 * wino_plane_units<GEOM>(); }
 template <int GEOM>
 constexpr int wino_smem_bytes() { return 2 * wino_stage_units<GEOM>() * 16; }
+// tile t (0 ... 31) of the wave with tile half mh: (image of the block, tile row, tile column).  The lane groups of a ds_read_b128 are the
+// 4-lane chunks c = t >> 2 in {0, 3, 5, 6} | {1, 2, 4, 7} (even | odd number of set bits); a group takes tile rows c >> 1 = 0 ... 3 of
+//   GEOM 0: one half of the tile columns (WinoGeom<0>);   GEOM 1: one of the wave's two images (WinoGeom<1>);
+//   GEOM 2: lanes in plain order (image, row, column).
+template <int GEOM>
+__host__ __device__ constexpr void wino_tile(int mh, int t, int& ti, int& ty, int& tx) {
+    const int c = t >> 2, odd = (c ^ (c >> 1) ^ (c >> 2)) & 1;
+    if (GEOM == 0) { ti = 0; ty = 4 * mh + (c >> 1); tx = 4 * odd + (t & 3); }
+    else if (GEOM == 1) { ti = 2 * mh + odd; ty = c >> 1; tx = t & 3; }
+    else { ti = 2 * mh + (t >> 4); ty = (t >> 2) & 3; tx = t & 3; }
+}
+// The two conflict-freedom claims of the layouts as compile-time facts: the 16 tiles of every ds_read_b128 lane group (lanes 16 g ... 16 g + 15
+// of a wave: chunk set g & 1 of the tile half mh) lie in 16 different units mod 16, and so do the 8 channel quads of a pixel.
+template <int GEOM>
+constexpr bool wino_geom_conflict_free() {
+    using G = WinoGeom<GEOM>;
+    for (int mh = 0; mh < 2; ++mh)
+        for (int set = 0; set < 2; ++set) {
+            unsigned seen = 0;
+            for (int t = 0; t < 32; ++t) {
+                const int c = t >> 2;
+                if (((c ^ (c >> 1) ^ (c >> 2)) & 1) != set) continue;
+                int ti = 0, ty = 0, tx = 0;
+                wino_tile<GEOM>(mh, t, ti, ty, tx);
+                seen |= 1u << ((G::image_offset(ti) + 2 * ty * G::kRowPitch + tx) & 15);
+            }
+            if (seen != 0xffffu) return false;
+        }
+    unsigned quads = 0;
+    for (int cq = 0; cq < 8; ++cq) quads |= 1u << ((cq * G::kPlane) & 15);
+    return __builtin_popcount(quads) == 8;
+}
+static_assert(wino_geom_conflict_free<0>() && wino_geom_conflict_free<1>(), "stage-buffer layouts: patch reads and fill stores free of bank conflicts");
 
 // arguments of the one-launch-per-layer kernel (below) and its LDS budget: stages of STAGE_CH channels + a 64 KB exchange buffer of its own
-// (32-channel stages where they fit -- GEOM 0 -- and the layer has whole ones; 16 otherwise: wino_layer_stage_channels)
+// (32-channel stages where they fit -- GEOM 0 and the mosaic of GEOM 1 -- and the layer has whole ones; 16 otherwise: wino_layer_stage_channels)
 struct ConvWinoLayerArgs {
     ConvWinoArgs c;          // (U, eh, ew, mode unused)
     const float* U4[4];      // index 2 eh + ew
@@ -126,9 +187,17 @@ template <int GEOM, int STAGE_CH = 16>
 constexpr int wino_layer_stage_bytes() { return 2 * (STAGE_CH / 4) * wino_plane_units<GEOM>() * 16; }
 template <int GEOM, int STAGE_CH = 16>
 constexpr int wino_layer_smem_bytes() { return wino_layer_stage_bytes<GEOM, STAGE_CH>() + 4 * 64 * 64 * 4; }
-static_assert(wino_layer_smem_bytes<0, 32>() <= 160 * 1024 && wino_layer_smem_bytes<1, 16>() <= 160 * 1024, "LDS of a compute unit");
-// (four 10 x 10 windows are 401 units densely packed: 32-channel stages of GEOM 1 would need 164 KB)
-inline int wino_layer_stage_channels(int geom, int Cin, bool stage32) { return stage32 && geom == 0 && Cin % 32 == 0 ? 32 : 16; }
+static_assert(wino_layer_smem_bytes<0, 32>() <= 160 * 1024 && wino_layer_smem_bytes<1, 32>() <= 160 * 1024 && wino_layer_smem_bytes<2, 16>() <= 160 * 1024, "LDS of a compute unit");
+// (four 10 x 10 windows of their own -- WinoGeom<2> -- are 401 units even densely packed: 32-channel stages would need 164 KB)
+// The kernel's geometry tag for a layer of block geometry `geom` (0 | 1, aae_host_types.h: Layer::wino_geom): the four-image blocks run on the
+// mosaic (WinoGeom<1>) when the halo is static and on windows of their own (WinoGeom<2>) otherwise.
+inline int wino_layer_geom_tag(int geom, bool static_halo) { return geom == 0 ? 0 : (static_halo ? 1 : 2); }
+// The static zero halo (WinoFillPlan<.., STATIC = true>) is the form of every launch whose blocks cover whole sub-images: four-image blocks
+// always, 16 x 16-pixel regions when the image has one.  Option "winograd_static_halo" = 0: the halo is loaded in every stage.
+inline bool wino_layer_static_halo(int geom, int blocks_x, int blocks_y, bool option) { return option && (geom != 0 || (blocks_x == 1 && blocks_y == 1)); }
+inline int wino_layer_stage_channels(int geom, int Cin, bool stage32, bool static_halo = true) {
+    return stage32 && (geom == 0 || static_halo) && Cin % 32 == 0 ? 32 : 16;
+}
 
 
 #ifndef AAE_WINO_DECLARATIONS_ONLY      // (the product library compiles the kernels below in a translation unit of their own: aae_wino.hip)
@@ -266,15 +335,6 @@ __device__ __forceinline__ WinoBlock wino_block(int block, int nbn, int blocks_x
     wino_block_geometry<GEOM>(w.region, blocks_x, blocks_y, w);
     return w;
 }
-// tile t (0 ... 31) of the wave with tile half mh: (image of the block, tile row, tile column)
-template <int GEOM>
-__device__ __forceinline__ void wino_tile(int mh, int t, int& ti, int& ty, int& tx) {
-    // GEOM 0: the lane groups of a ds_read_b128 are the 4-lane chunks c = t >> 2 in {0, 3, 5, 6} | {1, 2, 4, 7} (even | odd number of set
-    // bits): a group takes tile rows c >> 1 = 0 ... 3 of one half of the tile columns (WinoGeom<0>).
-    if (GEOM == 0) { const int c = t >> 2; ti = 0; ty = 4 * mh + (c >> 1); tx = 4 * ((c ^ (c >> 1) ^ (c >> 2)) & 1) + (t & 3); }
-    else { ti = 2 * mh + (t >> 4); ty = (t >> 2) & 3; tx = t & 3; }
-}
-
 
 // ---- what an instruction costs next to the fp32 matrix stream (tools/ubench/mfma_coissue.hip, profiles/r15/mfma_coissue.jsonl) ----------
 // v_mfma_f32_32x32x2_f32 holds a SIMD's matrix pipe for 64 cycles; two waves per SIMD keep it busy (0.999) as long as NOTHING else is
@@ -286,51 +346,154 @@ __device__ __forceinline__ void wino_tile(int mh, int t, int& ti, int& ty, int& 
 
 // A thread's share of a stage fill: source offsets (for the polyphase component (0, 0): the others lie a constant further, added as the
 // scalar part of the load) and LDS slots.  The same for every stage and every component of a block: computed once per block.
-template <int GEOM, int STAGE_CH, int NT>
+// STATIC (the static zero halo): the block's region is the whole sub-image, so the window's outermost rows and columns lie outside the image
+// in every stage of every component (the frame-to-source map does not depend on the component).  The slots then cover the (kRows - 2) x
+// (kCols - 2) data positions only -- a whole number per thread: no partly filled wave, no spare units -- and the block writes the zeros ONCE,
+// into both stage buffers, before its first fill (wino_zero_halo).  conv3: 2048 instead of 2592 float4 per 32-channel stage, 4 instead of 6
+// per thread; conv4: 2048 per 32 channels instead of 2 x 1600.
+template <int GEOM, int STAGE_CH, int NT, bool STATIC = false>
 struct WinoFillPlan {
+    using G = WinoGeom<GEOM>;
     static constexpr int kQuads = STAGE_CH / 4, kParts = STAGE_CH / 16;
-    static constexpr int kStageQuads = WinoGeom<GEOM>::kImages * WinoGeom<GEOM>::kRows * WinoGeom<GEOM>::kCols * kQuads;
+    static constexpr int kDataRows = G::kRows - 2, kDataCols = G::kCols - 2;
+    static constexpr int kStageQuads = G::kImages * (STATIC ? kDataRows * kDataCols : G::kRows * G::kCols) * kQuads;
     static constexpr int kPer = ((kStageQuads + NT - 1) / NT + kParts - 1) / kParts;       // float4 per thread and part
+    static_assert(!STATIC || kStageQuads % (NT * kParts) == 0, "static halo: every thread has the same number of slots");
+    static_assert(STATIC || GEOM != 1, "the mosaic's shared zero row needs the static halo");
     uint32_t goff[kParts * kPer];
     int lslot[kParts * kPer];
     // Slot i of thread t is float4 t + NT i of the stage: whole waves have it, one wave at most has it in part of its lanes (those beyond the
     // stage store zeros to spare units of the stage buffer: no lane of a storing wave is masked off), the waves behind have none.
-    __host__ __device__ static constexpr bool wave_stores(int wave, int i) { return wave * 64 + NT * i < kStageQuads; }
+    __host__ __device__ static constexpr bool wave_stores(int wave, int i) { return STATIC || wave * 64 + NT * i < kStageQuads; }
     // the spare unit of lane number `d` beyond the stage: column kCols / 2 of window row d / kQuads, which lies inside the row pitch and
     // which no pixel is stored to and no patch read touches (a different unit per lane)
-    static constexpr int kSpareColumn = (WinoGeom<GEOM>::kCols + 1) / 2;
-    static_assert(kSpareColumn < WinoGeom<GEOM>::kRowPitch && 64 / kQuads <= 2 * WinoGeom<GEOM>::kRows && NT % kQuads == 0, "spare units of the stage buffer");
+    static constexpr int kSpareColumn = (G::kCols + 1) / 2;
+    static_assert(STATIC || (kSpareColumn < G::kRowPitch && 64 / kQuads <= 2 * G::kRows), "spare units of the stage buffer");
+    static_assert(NT % kQuads == 0, "a pixel's quads in one slot round");
+    // STATIC: the halo positions of the frame, numbered -- whole frame rows first, then the zero columns of the data rows
+    static constexpr int kHaloRows = G::kFrameRows - (G::kFrameRows / (kDataRows + 1)) * kDataRows;       // 2 | 3
+    static constexpr int kHaloCols = G::kFrameCols - (G::kFrameCols / (kDataCols + 2)) * kDataCols;       // 2 | 4
+    static constexpr int kHalo = kHaloRows * G::kFrameCols + (G::kFrameRows - kHaloRows) * kHaloCols;
+    static_assert(!STATIC || kHalo + G::kImages * kDataRows * kDataCols == G::kFrameRows * G::kFrameCols, "halo + data = the frame");
 };
 constexpr uint32_t kWinoOutside = 0x80000000u;      // a lane offset beyond every buffer view: the load returns zeros ('SAME' padding, empty image slots)
-template <int GEOM, int STAGE_CH, int NT>
-__device__ __forceinline__ void wino_fill_plan(const ConvWinoArgs& a, const WinoBlock& wb, WinoFillPlan<GEOM, STAGE_CH, NT>& f) {
+// unit of frame position (fy, fx) inside a channel quad's plane
+template <int GEOM>
+__host__ __device__ constexpr int wino_frame_unit(int fy, int fx) { return (fx & 1) * WinoGeom<GEOM>::kParityPitch + fy * WinoGeom<GEOM>::kRowPitch + (fx >> 1); }
+// STATIC: data pixel number p (0 ... kImages x kDataRows x kDataCols - 1) of the fill order -> frame position.  With 8 quads per pixel (32-channel
+// stages) the 8-lane groups of a ds_write_b128 are the quads of one pixel, in plain order (image, row, column).  With 4 quads (16-channel
+// stages) a group holds two pixels, which must lie 4 units (mod 8) apart for the quads' planes (1 | 5 mod 8) to miss each other: bit 0 of p is
+// column bit 3 for GEOM 0 (8 columns = 4 units on) and row bit 1 for GEOM 1 (2 rows = 20 units on).  (Global memory sees 64 contiguous bytes per pixel either way.)
+template <int GEOM, int QUADS>
+__host__ __device__ constexpr void wino_fill_pixel(int p, int& fy, int& fx) {
     using G = WinoGeom<GEOM>;
-    using F = WinoFillPlan<GEOM, STAGE_CH, NT>;
+    constexpr int DR = G::kRows - 2, DC = G::kCols - 2;
+    int wi = p / (DR * DC), dy = p % (DR * DC) / DC, dx = p % DC;
+    if (QUADS == 4 && GEOM == 0) {
+        const int q = p >> 1;
+        wi = 0; dy = q / (DC / 2); dx = (q % (DC / 2)) + (p & 1) * (DC / 2);
+    } else if (QUADS == 4) {
+        const int q = p >> 1, r = q / DC;                       // r: (image, row bit 2, row bit 0)
+        wi = r >> 2; dy = (r & 1) + 2 * (p & 1) + 4 * ((r >> 1) & 1); dx = q % DC;
+    }
+    fy = G::frame_row(wi) + 1 + dy;
+    fx = G::frame_col(wi) + 1 + dx;
+}
+template <int GEOM, int QUADS>
+constexpr bool wino_fill_order_valid() {
+    using G = WinoGeom<GEOM>;
+    constexpr int DR = G::kRows - 2, DC = G::kCols - 2, N = G::kImages * DR * DC;
+    bool seen[G::kFrameRows * G::kFrameCols] = {};
+    for (int p = 0; p < N; ++p) {
+        int fy = 0, fx = 0;
+        wino_fill_pixel<GEOM, QUADS>(p, fy, fx);
+        if (seen[fy * G::kFrameCols + fx]) return false;       // (N different data positions: a permutation)
+        seen[fy * G::kFrameCols + fx] = true;
+    }
+    for (int p = 0; p < N; p += 8 / QUADS) {                   // an 8-lane store group: its units differ mod 8
+        unsigned banks = 0;
+        for (int l = 0; l < 8; ++l) {
+            int fy = 0, fx = 0;
+            wino_fill_pixel<GEOM, QUADS>(p + l / QUADS, fy, fx);
+            banks |= 1u << ((wino_frame_unit<GEOM>(fy, fx) + (l % QUADS) * G::kPlane) & 7);
+        }
+        if (banks != 0xffu) return false;
+    }
+    return true;
+}
+static_assert(wino_fill_order_valid<0, 8>() && wino_fill_order_valid<0, 4>() && wino_fill_order_valid<1, 8>() && wino_fill_order_valid<1, 4>(),
+              "static-halo fill order: every data position once, store groups free of bank conflicts");
+
+template <int GEOM, int STAGE_CH, int NT, bool STATIC>
+__device__ __forceinline__ void wino_fill_plan(const ConvWinoArgs& a, const WinoBlock& wb, WinoFillPlan<GEOM, STAGE_CH, NT, STATIC>& f) {
+    using G = WinoGeom<GEOM>;
+    using F = WinoFillPlan<GEOM, STAGE_CH, NT, STATIC>;
     constexpr int kPlane = wino_plane_units<GEOM>();
     const int cq_per_pixel = a.Cin / 4;
-    // slot 0 by division, the others by walking on: NT / kQuads pixels = (kStepI images, kStepY rows, kStepX columns) further, with carries
-    constexpr int kStep = NT / F::kQuads, kWindow = G::kRows * G::kCols;
-    constexpr int kStepI = kStep / kWindow, kStepY = kStep % kWindow / G::kCols, kStepX = kStep % G::kCols;
-    const int pixel0 = (int)threadIdx.x / F::kQuads, cq = (int)threadIdx.x % F::kQuads;
-    int wi = pixel0 / kWindow, wy = pixel0 % kWindow / G::kCols, wx = pixel0 % G::kCols;
+    if constexpr (STATIC) {
+        // (the region is the whole sub-image: wy0 = wx0 = -1, Ho = kDataRows, Wo = kDataCols -- every slot lies inside its image)
+        const int cq = (int)threadIdx.x % F::kQuads;
 #pragma unroll
-    for (int i = 0; i < F::kParts * F::kPer; ++i) {
-        const int idx = (int)threadIdx.x + NT * i;
-        f.goff[i] = kWinoOutside;
-        if (idx < F::kStageQuads) {
-            const int uu = wb.wy0 + wy, vv = wb.wx0 + wx, b = wb.img0 + wi;
-            if (uu >= 0 && uu < a.Ho && vv >= 0 && vv < a.Wo && b < a.B)
-                f.goff[i] = (uint32_t)(((((size_t)b * a.H + 2 * uu) * a.W + 2 * vv) * cq_per_pixel + cq) * 16);
-            f.lslot[i] = cq * kPlane + wi * G::kImagePitch + (wx & 1) * G::kParityPitch + wy * G::kRowPitch + (wx >> 1);
-        } else {
-            const int d = (idx - F::kStageQuads) & 63, row = d / F::kQuads;       // (only the lanes of the one partly filled wave ever store there)
-            f.lslot[i] = cq * kPlane + (row / G::kRows) * G::kParityPitch + (row % G::kRows) * G::kRowPitch + F::kSpareColumn;
+        for (int i = 0; i < F::kParts * F::kPer; ++i) {
+            const int p = ((int)threadIdx.x + NT * i) / F::kQuads, wi = p / (F::kDataRows * F::kDataCols), b = wb.img0 + wi;
+            int fy, fx;
+            wino_fill_pixel<GEOM, F::kQuads>(p, fy, fx);
+            const int uu = fy - G::frame_row(wi) - 1, vv = fx - G::frame_col(wi) - 1;
+            f.goff[i] = b < a.B ? (uint32_t)(((((size_t)b * a.H + 2 * uu) * a.W + 2 * vv) * cq_per_pixel + cq) * 16) : kWinoOutside;
+            f.lslot[i] = cq * kPlane + wino_frame_unit<GEOM>(fy, fx);
         }
-        wx += kStepX;
-        wy += kStepY + (wx >= G::kCols ? 1 : 0);
-        wx -= wx >= G::kCols ? G::kCols : 0;
-        wi += kStepI + (wy >= G::kRows ? 1 : 0);
-        wy -= wy >= G::kRows ? G::kRows : 0;
+    } else {
+        // slot 0 by division, the others by walking on: NT / kQuads pixels = (kStepI images, kStepY rows, kStepX columns) further, with carries
+        constexpr int kStep = NT / F::kQuads, kWindow = G::kRows * G::kCols;
+        constexpr int kStepI = kStep / kWindow, kStepY = kStep % kWindow / G::kCols, kStepX = kStep % G::kCols;
+        const int pixel0 = (int)threadIdx.x / F::kQuads, cq = (int)threadIdx.x % F::kQuads;
+        int wi = pixel0 / kWindow, wy = pixel0 % kWindow / G::kCols, wx = pixel0 % G::kCols;
+#pragma unroll
+        for (int i = 0; i < F::kParts * F::kPer; ++i) {
+            const int idx = (int)threadIdx.x + NT * i;
+            f.goff[i] = kWinoOutside;
+            if (idx < F::kStageQuads) {
+                const int uu = wb.wy0 + wy, vv = wb.wx0 + wx, b = wb.img0 + wi;
+                if (uu >= 0 && uu < a.Ho && vv >= 0 && vv < a.Wo && b < a.B)
+                    f.goff[i] = (uint32_t)(((((size_t)b * a.H + 2 * uu) * a.W + 2 * vv) * cq_per_pixel + cq) * 16);
+                f.lslot[i] = cq * kPlane + wi * G::kImagePitch + (wx & 1) * G::kParityPitch + wy * G::kRowPitch + (wx >> 1);
+            } else {
+                const int d = (idx - F::kStageQuads) & 63, row = d / F::kQuads;       // (only the lanes of the one partly filled wave ever store there)
+                f.lslot[i] = cq * kPlane + (row / G::kRows) * G::kParityPitch + (row % G::kRows) * G::kRowPitch + F::kSpareColumn;
+            }
+            wx += kStepX;
+            wy += kStepY + (wx >= G::kCols ? 1 : 0);
+            wx -= wx >= G::kCols ? G::kCols : 0;
+            wi += kStepI + (wy >= G::kRows ? 1 : 0);
+            wy -= wy >= G::kRows ? G::kRows : 0;
+        }
+    }
+}
+// STATIC: the zeros of the halo, once per block, into BOTH stage buffers and all channel quads.  Every unit of the frame that a patch read
+// touches is either a data position (a fill slot of every stage) or one of these; nothing stores to them afterwards.  Ordered before the first
+// patch read by the barrier that ends wino_first_stage.
+template <int GEOM, int STAGE_CH, int NT>
+__device__ __forceinline__ void wino_zero_halo(f32x4* lds) {
+    using G = WinoGeom<GEOM>;
+    using F = WinoFillPlan<GEOM, STAGE_CH, NT, true>;
+    constexpr int kStage = F::kQuads * wino_plane_units<GEOM>(), kTotal = 2 * F::kQuads * F::kHalo;
+    constexpr int kRowPart = F::kHaloRows * G::kFrameCols, kRowStep = (G::kFrameRows - 1) / (F::kHaloRows - 1);
+#pragma unroll
+    for (int i = 0; i < (kTotal + NT - 1) / NT; ++i) {
+        const int idx = (int)threadIdx.x + NT * i;
+        if (idx < kTotal) {
+            const int hq = idx % (F::kQuads * F::kHalo), buf = idx / (F::kQuads * F::kHalo), cq = hq % F::kQuads, hp = hq / F::kQuads;
+            int fy, fx;
+            if (hp < kRowPart) {                                 // the zero rows 0, kRowStep, ...
+                fy = (hp / G::kFrameCols) * kRowStep;
+                fx = hp % G::kFrameCols;
+            } else {                                             // the zero columns of the data rows: the first and last column of every image
+                const int k = hp - kRowPart, r = k / F::kHaloCols, c = k % F::kHaloCols;
+                fy = 1 + r + r / F::kDataRows;
+                fx = (c >> 1) * (F::kDataCols + 2) + (c & 1) * (F::kDataCols + 1);
+            }
+            lds[buf * kStage + cq * wino_plane_units<GEOM>() + wino_frame_unit<GEOM>(fy, fx)] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     }
 }
 
@@ -348,15 +511,16 @@ __device__ __forceinline__ void wino_first_fragments(const ConvWinoArgs& a, cons
     for (int p = 0; p < 2 * PB; ++p) u[p] = buffer_load4_s(urs, ulane + (p % PB) * 1024u, two_rows ? (p / PB) * PB * 1024u : (p / PB) * (NP * 1024u));
 }
 // The first stage of a block's first component (parities eh, ew) into stage buffer 0; ends behind a block barrier.
-template <int GEOM, int STAGE_CH, int NT>
-__device__ __forceinline__ void wino_first_stage(const ConvWinoArgs& a, int eh, int ew, const WinoFillPlan<GEOM, STAGE_CH, NT>& fill, f32x4* lds) {
-    using F = WinoFillPlan<GEOM, STAGE_CH, NT>;
+template <int GEOM, int STAGE_CH, int NT, bool STATIC>
+__device__ __forceinline__ void wino_first_stage(const ConvWinoArgs& a, int eh, int ew, const WinoFillPlan<GEOM, STAGE_CH, NT, STATIC>& fill, f32x4* lds) {
+    using F = WinoFillPlan<GEOM, STAGE_CH, NT, STATIC>;
     const int wave = wave_uniform((int)threadIdx.x >> 6);
     const buffer_rsrc xrs = make_buffer(a.x, (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 4));
     const uint32_t parity_off = (uint32_t)(((size_t)eh * a.W + ew) * a.Cin * 4);
     f32x4 stg[F::kParts * F::kPer];
 #pragma unroll
     for (int i = 0; i < F::kParts * F::kPer; ++i) stg[i] = buffer_load4_s(xrs, fill.goff[i], parity_off);
+    if constexpr (STATIC) wino_zero_halo<GEOM, STAGE_CH, NT>(lds);       // (under the loads' flight)
 #pragma unroll
     for (int i = 0; i < F::kParts * F::kPer; ++i)
         if (F::wave_stores(wave, i)) lds[fill.lslot[i]] = stg[i];
@@ -372,12 +536,12 @@ __device__ __forceinline__ void wino_first_stage(const ConvWinoArgs& a, int eh, 
 // CHAIN (the one-launch-per-layer kernel): bit 0 -- the first stage of this component already lies in stage buffer `buf0` and `uin` holds the
 // weight fragments of units 0 and 1 (the previous component fetched them); bit 1 -- this component does the same for the next one (taps NTA x
 // NTB, weights Un, parities neh / new_): its first stage is loaded during the last stage here, its first fragments behind the last burst.
-template <int TA, int TB, bool SWAP, int GEOM, int STAGE_CH, bool ACCUMULATE, bool WIDE, int CHAIN = 0, int NTA = 3, int NTB = 3>
+template <int TA, int TB, bool SWAP, int GEOM, int STAGE_CH, bool ACCUMULATE, bool WIDE, int CHAIN = 0, int NTA = 3, int NTB = 3, bool STATIC = false>
 __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const float* U, int eh, int ew, const WinoBlock& wb, f32x4* lds, float* xch_all,
-                                                const WinoFillPlan<GEOM, STAGE_CH, WIDE ? 256 : 512>& fill, int& buf0, f32x4 (&uin)[8],
+                                                const WinoFillPlan<GEOM, STAGE_CH, WIDE ? 256 : 512, STATIC>& fill, int& buf0, f32x4 (&uin)[8],
                                                 const float* Un, int neh, int new_, f32x4 (&uout)[8]) {
     using G = WinoGeom<GEOM>;
-    using F = WinoFillPlan<GEOM, STAGE_CH, WIDE ? 256 : 512>;
+    using F = WinoFillPlan<GEOM, STAGE_CH, WIDE ? 256 : 512, STATIC>;
     constexpr int PB = TB + 1;                                  // points (= patch positions) along B
     constexpr int kQuads = STAGE_CH / 4, kGroups = STAGE_CH / 8;                    // channel quads / 8-channel groups per stage
     constexpr int kPlane = wino_plane_units<GEOM>(), kStage = kQuads * kPlane;
@@ -385,6 +549,7 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
     constexpr int kParts = F::kParts, kPer = F::kPer;           // the fill of the next stage happens in this many parts (few staging registers live at a time)
     constexpr int NH = WIDE ? 2 : 1;                            // 32-channel halves per wave
     constexpr int kOffA = TA == 2 ? 1 : 0, kOffB = TB == 2 ? 1 : 0;   // a 2-tap dimension starts one sample into the window
+    static_assert(!STATIC || (CHAIN & 1), "the static halo is written in front of the chained form's first stage (wino_first_stage)");
     static_assert(CHAIN == 0 || !WIDE, "the chained form passes one wave's weight fragments between the components");
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);        // (a scalar: every choice by wave below is a branch, not a select)
     const int mh = wave & 1, nh = WIDE ? 0 : (wave >> 1) & 1, ph = WIDE ? wave >> 1 : wave >> 2, m = lane & 31, h = lane >> 5;
@@ -429,7 +594,7 @@ __device__ __forceinline__ void wino_phase_body(const ConvWinoArgs& a, const flo
     //        F(2, 2)  ph 0: positions (0, -, 1)          -> rows 0, 1 (d0 - d1, d1)              ph 1: (1, -, 2) -> row 2 (d1 - d2)
     auto fA = [](int pos) { return SWAP ? (pos & 1) * kParity + (pos >> 1) : pos * G::kRowPitch; };
     auto fB = [](int pos) { return SWAP ? pos * G::kRowPitch : (pos & 1) * kParity + (pos >> 1); };
-    const int lane_base = li * G::kImagePitch + 2 * lty * G::kRowPitch + ltx;
+    const int lane_base = G::image_offset(li) + 2 * lty * G::kRowPitch + ltx;
     const int posA0 = (TA == 3 ? (ph == 0 ? 0 : 2) : (ph == 0 ? 0 : 1)) + kOffA;
     const int posA1 = (ph == 0 ? 1 : 3) + kOffA;                 // (F(2, 3) only)
     const int posA2 = (TA == 3 ? (ph == 0 ? 2 : 1) : (ph == 0 ? 1 : 2)) + kOffA;
@@ -748,23 +913,24 @@ __global__ __launch_bounds__(512) void conv_wino_phase_kernel(ConvWinoArgs a) {
 #endif
 
 // ---- one launch per LAYER: the four phases one behind the other in the block (3 x 3, 3 x 2, 2 x 3, 2 x 2 taps), their outputs added
-//      up in an exchange buffer of its own (64 KB behind the stage buffers: stages of STAGE_CH = 32 channels for GEOM 0, 16 for GEOM 1 -- wino_layer_stage_channels); the
+//      up in an exchange buffer of its own (64 KB behind the stage buffers: stages of STAGE_CH = 32 channels for GEOM 0 and 1, 16 for GEOM 2 -- wino_layer_stage_channels); the
 //      output is written once, with bias / ReLU / BN.  No read-modify-write of the output tensor, one prologue / epilogue per four phases.
 //      The phases are CHAINED: each fetches the next one's first stage and first weight fragments while its own K loop ends, so that only
 //      the first phase of a block waits for global memory with an empty matrix pipe.
-template <int GEOM, bool WIDE, int STAGE_CH>
+template <int GEOM, bool WIDE, int STAGE_CH, bool STATIC>
 __device__ __forceinline__ void wino_layer_block(const ConvWinoArgs& a, const float* const (&U4)[4], const WinoBlock& wb, unsigned char* smem_raw) {
     constexpr int SC = STAGE_CH;
     static_assert(SC == 16 || (SC == 32 && !WIDE), "stage size");
+    static_assert(!STATIC || !WIDE, "the static halo belongs to the chained form");
     f32x4* lds = reinterpret_cast<f32x4*>(smem_raw);
     float* xch = reinterpret_cast<float*>(smem_raw + wino_layer_stage_bytes<GEOM, SC>());
-    WinoFillPlan<GEOM, SC, WIDE ? 256 : 512> fill;
+    WinoFillPlan<GEOM, SC, WIDE ? 256 : 512, STATIC> fill;
     int buf0 = 0;
     f32x4 ua[8], ub[8];
     // (the first weight fragments are on their way while the fill plan is built: they depend on nothing but the block's column block)
     if (!WIDE) wino_first_fragments<3, 3>(a, U4[3], wb, ua);
     wino_fill_plan(a, wb, fill);
-    if (WIDE) {
+    if constexpr (WIDE) {
         wino_phase_body<3, 3, false, GEOM, SC, false, WIDE>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
         wino_phase_body<3, 2, false, GEOM, SC, true, WIDE>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
         wino_phase_body<3, 2, true, GEOM, SC, true, WIDE>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, nullptr, 0, 0, ub);
@@ -772,21 +938,21 @@ __device__ __forceinline__ void wino_layer_block(const ConvWinoArgs& a, const fl
     } else {
         constexpr bool W = WIDE;        // (false here: the chained form)
         if (!W) wino_first_stage(a, 1, 1, fill, lds);
-        wino_phase_body<3, 3, false, GEOM, SC, false, W, W ? 0 : 3, 3, 2>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, U4[2], 1, 0, ub);
-        wino_phase_body<3, 2, false, GEOM, SC, true, W, W ? 0 : 3, 3, 2>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ub, U4[1], 0, 1, ua);
-        wino_phase_body<3, 2, true, GEOM, SC, true, W, W ? 0 : 3, 2, 2>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, U4[0], 0, 0, ub);
-        wino_phase_body<2, 2, false, GEOM, SC, true, W, W ? 0 : 1>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ub, nullptr, 0, 0, ua);
+        wino_phase_body<3, 3, false, GEOM, SC, false, W, W ? 0 : 3, 3, 2, STATIC>(a, U4[3], 1, 1, wb, lds, xch, fill, buf0, ua, U4[2], 1, 0, ub);
+        wino_phase_body<3, 2, false, GEOM, SC, true, W, W ? 0 : 3, 3, 2, STATIC>(a, U4[2], 1, 0, wb, lds, xch, fill, buf0, ub, U4[1], 0, 1, ua);
+        wino_phase_body<3, 2, true, GEOM, SC, true, W, W ? 0 : 3, 2, 2, STATIC>(a, U4[1], 0, 1, wb, lds, xch, fill, buf0, ua, U4[0], 0, 0, ub);
+        wino_phase_body<2, 2, false, GEOM, SC, true, W, W ? 0 : 1, 3, 3, STATIC>(a, U4[0], 0, 0, wb, lds, xch, fill, buf0, ub, nullptr, 0, 0, ua);
     }
     wino_store_block<GEOM, WIDE ? 256 : 512>(a, 3, wb, xch);
 }
 
-template <int GEOM, bool WIDE, int STAGE_CH = 16>
+template <int GEOM, bool WIDE, int STAGE_CH = 16, bool STATIC = false>
 __global__ __launch_bounds__(WIDE ? 256 : 512) void conv_wino_layer_kernel(ConvWinoLayerArgs p) {
     AAE_DYN_SMEM(smem_raw);
     const ConvWinoArgs& a = p.c;
     const WinoBlock wb = wino_block<GEOM>(blockIdx.x, a.Cout / 64, a.blocks_x, a.blocks_y, a.regions, a.xcd_cols);
     if (!wb.live) return;
-    wino_layer_block<GEOM, WIDE, STAGE_CH>(a, p.U4, wb, smem_raw);
+    wino_layer_block<GEOM, WIDE, STAGE_CH, STATIC>(a, p.U4, wb, smem_raw);
 #ifdef AAE_WINO_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     AAE_WINO_STAMP(a, 16);
@@ -796,7 +962,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 512) void conv_wino_layer_kernel(ConvW
 
 // ---- the same launch over several objects (ConvWinoMultiArgs): a block finds the object its region belongs to and runs exactly the
 //      single-object block on that object's tensors -- bit-identical to the object's own launch.
-template <int GEOM, int STAGE_CH = 16>
+template <int GEOM, int STAGE_CH = 16, bool STATIC = false>
 __global__ __launch_bounds__(512) void conv_wino_layer_multi_kernel(ConvWinoMultiArgs p) {
     AAE_DYN_SMEM(smem_raw);
     WinoBlock wb;
@@ -808,7 +974,7 @@ __global__ __launch_bounds__(512) void conv_wino_layer_multi_kernel(ConvWinoMult
     const ConvWinoObject& ob = p.obj[o];
     a.x = ob.x; a.out = ob.out; a.bias = ob.bias; a.bn_scale = ob.bn_scale; a.bn_shift = ob.bn_shift; a.B = ob.B;
     const float* U4[4] = {ob.U4[0], ob.U4[1], ob.U4[2], ob.U4[3]};
-    wino_layer_block<GEOM, false, STAGE_CH>(a, U4, wb, smem_raw);
+    wino_layer_block<GEOM, false, STAGE_CH, STATIC>(a, U4, wb, smem_raw);
 }
 
 #endif  // AAE_WINO_DECLARATIONS_ONLY

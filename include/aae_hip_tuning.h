@@ -53,6 +53,10 @@
  *   "winograd_xcd_cols" (-1): 64-column blocks of a window region that share an XCD (-1 = per layer: all of them up to four; 0 = plain block order)
  *   "winograd_stage32" (1): the layer kernel's K loop in stages of 32 input channels where the stage buffers fit beside the exchange buffer (16 x 16-pixel
  *                        regions: conv2, conv3) and 32 | Cin; 0 = 16-channel stages everywhere (bit-identical answers, twice the stage barriers)
+ *   "winograd_static_halo" (1): where a block's window region is the whole sub-image (conv3: one 16 x 16-pixel region per image; conv4: four 8 x 8 images per block) the
+ *                        zero halo of the 'SAME' padding is written to the stage buffers once per block and the stage fill moves the data positions only; with it the
+ *                        four-image blocks lie on one 19 x 20 mosaic, which leaves room for 32-channel stages.  0 = the halo is loaded in every stage, four-image
+ *                        blocks in 16-channel stages (bit-identical answers)
  *   "multi_split_items" (1): aae_encode_nn_multi -- a class with 5 ... 8 boxes in the frame (up to 12 when no other class has more than 4) joins the per-detection group as items of
  *                        at most 4 boxes; 0 = such a class is a mid-batch candidate / its own call.  Needs "multi_group_plan" = 1
  *   "multi_group_winograd" (1): aae_encode_nn_multi -- in a group of objects with 1 ... 4 detections each a conv layer runs as one Winograd launch across the objects where the

@@ -35,11 +35,14 @@ int main(int argc, char** argv) {
     const int B = argc > 1 ? atoi(argv[1]) : 256;
     const int reps = argc > 2 ? atoi(argv[2]) : 10;
     const int only_cols = argc > 3 ? atoi(argv[3]) : -1;         // >= 0: only the mappings with this xcd_cols (or the layer's largest valid one below it)
-    const bool stage32 = argc > 4 ? atoi(argv[4]) != 0 : true;   // 32-channel stages where the layer takes them (conv2, conv3); 0 = 16-channel stages everywhere
+    const bool stage32 = argc > 4 ? atoi(argv[4]) != 0 : true;   // 32-channel stages where the layer takes them; 0 = 16-channel stages everywhere
+    const bool halo = argc > 5 ? atoi(argv[5]) != 0 : true;      // the static zero halo where the blocks cover whole sub-images (conv3, conv4); 0 = loaded in every stage
     struct Shape { const char* name; int H, Cin, Cout, geom; } shapes[3] = {{"conv2", 64, 128, 256, 0}, {"conv3", 32, 256, 512, 0}, {"conv4", 16, 512, 512, 1}};
-    CHECK(hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0>()));
-    CHECK(hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<0, false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<0, 32>()));
-    CHECK(hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<1>()));
+    // the instantiations of the library's launch wrapper (aae_wino_launch.h): (geometry tag, stage channels, static halo)
+#define WINO_FORMS(X) X(0, 16, false) X(0, 32, false) X(0, 16, true) X(0, 32, true) X(1, 16, true) X(1, 32, true) X(2, 16, false)
+#define WINO_X(G, SC, ST) CHECK(hipFuncSetAttribute((const void*)aae::conv_wino_layer_kernel<G, false, SC, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::wino_layer_smem_bytes<G, SC>()));
+    WINO_FORMS(WINO_X)
+#undef WINO_X
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
     unsigned long long seed = 0x9E3779B97F4A7C15ull;
@@ -83,11 +86,13 @@ int main(int argc, char** argv) {
             CHECK(hipMemset(dst, 0, nstamp * 8));
             p.c.stamps = dst;
 #endif
+            const bool st = aae::wino_layer_static_halo(s.geom, p.c.blocks_x, p.c.blocks_y, halo);
+            const int tag = aae::wino_layer_geom_tag(s.geom, st), sc = aae::wino_layer_stage_channels(s.geom, s.Cin, stage32, st);
             auto launch = [&]() {
-                if (aae::wino_layer_stage_channels(s.geom, s.Cin, stage32) == 32)
-                    hipLaunchKernelGGL((aae::conv_wino_layer_kernel<0, false, 32>), dim3(grid), dim3(512), (aae::wino_layer_smem_bytes<0, 32>()), 0, p);
-                else if (s.geom == 0) hipLaunchKernelGGL((aae::conv_wino_layer_kernel<0, false>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<0>(), 0, p);
-                else hipLaunchKernelGGL((aae::conv_wino_layer_kernel<1, false>), dim3(grid), dim3(512), aae::wino_layer_smem_bytes<1>(), 0, p);
+#define WINO_X(G, SC, ST) \
+                if (tag == G && sc == SC && st == ST) hipLaunchKernelGGL((aae::conv_wino_layer_kernel<G, false, SC, ST>), dim3(grid), dim3(512), (aae::wino_layer_smem_bytes<G, SC>()), 0, p);
+                WINO_FORMS(WINO_X)
+#undef WINO_X
             };
             // warm up until the clocks have settled (the host-side set-up above leaves the GPU idle for seconds: the first ~100 ms after it run slow)
             for (int w = 0; w < (ci == 0 || only_cols >= 0 ? 60 : 10); ++w) launch();
@@ -99,8 +104,8 @@ int main(int argc, char** argv) {
             float ms = 0;
             CHECK(hipEventElapsedTime(&ms, e0, e1));
             ms /= reps;
-            printf("{\"what\": \"wino_layer_time\", \"var\": %d, \"B\": %d, \"layer\": \"%s\", \"stage_channels\": %d, \"xcd_cols\": %d, \"grid\": %u, \"ms\": %.4f, \"mfma_tflops\": %.1f, \"mfma_frac_of_157\": %.3f, \"tf_equivalent\": %.1f",
-                   AAE_WINO_VAR, B, s.name, aae::wino_layer_stage_channels(s.geom, s.Cin, stage32), xc, grid, ms, executed / (ms * 1e-3) / 1e12, executed / (ms * 1e-3) / 1e12 / 157.3, executed * 100.0 / 49.0 / (ms * 1e-3) / 1e12);
+            printf("{\"what\": \"wino_layer_time\", \"var\": %d, \"B\": %d, \"layer\": \"%s\", \"stage_channels\": %d, \"static_halo\": %d, \"xcd_cols\": %d, \"grid\": %u, \"ms\": %.4f, \"mfma_tflops\": %.1f, \"mfma_frac_of_157\": %.3f, \"tf_equivalent\": %.1f",
+                   AAE_WINO_VAR, B, s.name, sc, (int)st, xc, grid, ms, executed / (ms * 1e-3) / 1e12, executed / (ms * 1e-3) / 1e12 / 157.3, executed * 100.0 / 49.0 / (ms * 1e-3) / 1e12);
 #ifdef AAE_WINO_STAMPS
             std::vector<long long> hs(nstamp);
             CHECK(hipMemcpy(hs.data(), dst, nstamp * 8, hipMemcpyDeviceToHost));
