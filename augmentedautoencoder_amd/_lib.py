@@ -18,6 +18,7 @@ AAE_MAX_LAYERS = 8
 AAE_SCAN_AUTO, AAE_SCAN_GEMV, AAE_SCAN_MFMA, AAE_SCAN_STREAM, AAE_SCAN_STREAM_2L, AAE_SCAN_AUTO_NO_PRUNE, AAE_SCAN_STREAM_WALK = 0, 1, 2, 3, 4, 5, 6
 AAE_SCAN_AUTO_PACKED, AAE_SCAN_AUTO_RH2, AAE_SCAN_AUTO_FIN, AAE_SCAN_AUTO_TOPK_ROWS = 7, 8, 9, 10
 AAE_ABI_VERSION = 3
+AAE_MODEL_RECONST, AAE_MODEL_CAD = 0, 1
 
 LIB_NAME = 'libaae_hip.so'
 # the same sources with -DAAE_EXPERIMENTS: every kernel variant that measured slower than the defaults + the profiling / ablation
@@ -43,6 +44,8 @@ EXPORTED_SYMBOLS = (
     'aae_multi_workspace_bytes', 'aae_multi_rows', 'aae_encode_nn_multi', 'aae_codebook_nn_multi', 'aae_detect_nn_multi', 'aae_multi_last_launches',
     'aae_decoder_create', 'aae_decoder_destroy', 'aae_decoder_workspace_bytes', 'aae_decoder_forward',
     'aae_decoder_forward_timed', 'aae_decoder_kernel_label', 'aae_decoder_kernel_flops', 'aae_decoder_activation_info',
+    'aae_mesh_create', 'aae_mesh_destroy', 'aae_render_workspace_bytes', 'aae_render_embedding_views', 'aae_render_embedding_views_timed',
+    'aae_render_frames',
 )
 
 
@@ -70,6 +73,12 @@ class DecoderDesc(Structure):
         ('batch_norm', c_int32),
         ('bn_eps', c_float),
     ]
+
+
+class RenderParams(Structure):
+    """aae_render_params"""
+    _fields_ = [('K', c_double * 9), ('t', c_double * 3), ('W', c_int32), ('H', c_int32), ('clip_near', c_double), ('clip_far', c_double),
+                ('pad_factor', c_double), ('light', c_float * 3), ('ambient', c_float), ('diffuse', c_float), ('specular', c_float)]
 
 
 class MultiItem(Structure):
@@ -189,6 +198,27 @@ def declare(lib):
     return lib
 
 
+def declare_render(lib):
+    """The mesh rasteriser's entry points (aae_render.hip: part of the GPU library only, the CPU-emulated build of the host
+    sources that the tests load through declare() has no rasteriser)."""
+    lib.aae_mesh_create.restype = c_int
+    lib.aae_mesh_create.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, POINTER(c_void_p)]
+    lib.aae_mesh_destroy.restype = None
+    lib.aae_mesh_destroy.argtypes = [c_void_p]
+    lib.aae_render_workspace_bytes.restype = c_size_t
+    lib.aae_render_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    lib.aae_render_embedding_views.restype = c_int
+    lib.aae_render_embedding_views.argtypes = [c_void_p, c_void_p, c_int, POINTER(RenderParams), c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_size_t, c_void_p]
+    lib.aae_render_embedding_views_timed.restype = c_int
+    lib.aae_render_embedding_views_timed.argtypes = [c_void_p, c_void_p, c_int, POINTER(RenderParams), c_int, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_size_t, c_void_p, POINTER(c_float)]
+    lib.aae_render_frames.restype = c_int
+    lib.aae_render_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_int, POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -209,7 +239,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare(ctypes.CDLL(path))
+    lib = declare_render(declare(ctypes.CDLL(path)))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -2,10 +2,11 @@
 experiment with the HIP encoder (the reference's command: /root/reference/auto_pose/ae/ae_embed.py:17-93;
 BASELINE config 3).
 
-The reference renders the 92 232 views with its OpenGL renderer while embedding; rendering is out
-of scope here, so the views come from ``--views file.npy`` ([N,H,W,C] uint8, memory-mapped -- e.g.
-rendered once with the reference tooling) plus optional ``--bbs file.npy``, or ``--synthetic``
-(deterministic patterns, for benchmarking the encoder-only throughput)."""
+The reference renders the 92 232 views with its OpenGL renderer while embedding.  Here ``--render``
+renders them from [Paths] MODEL_PATH with the HIP rasteriser (meshrenderer.py), batch by batch on the
+device; or the views come from ``--views file.npy`` ([N,H,W,C] uint8, memory-mapped -- e.g. rendered
+once with the reference tooling) plus optional ``--bbs file.npy``, or ``--synthetic`` (deterministic
+patterns, for benchmarking the encoder-only throughput)."""
 from __future__ import annotations
 
 import argparse
@@ -17,7 +18,7 @@ import numpy as np
 from . import ae_factory as factory
 from . import session as S
 from . import utils as u
-from .dataset import SyntheticViewSource
+from .dataset import MeshViewSource, SyntheticViewSource
 
 
 def _parse(argv):
@@ -27,6 +28,7 @@ def _parse(argv):
     ap.add_argument('--views', default=None, help='[N,H,W,C] uint8 .npy holding the views to embed')
     ap.add_argument('--bbs', default=None, help='[N,4] object bounding boxes of those views (.npy)')
     ap.add_argument('--synthetic', action='store_true', help='embed deterministic synthetic views')
+    ap.add_argument('--render', action='store_true', help='render the views from [Paths] MODEL_PATH on the GPU')
     return ap.parse_args(argv)
 
 
@@ -39,8 +41,13 @@ def _attach_views(dataset, opts):
         dataset.set_view_source(lambda a, e, Rs: (np.ascontiguousarray(views[a:e]), boxes[a:e]))
     elif opts.synthetic:
         dataset.set_view_source(SyntheticViewSource(dataset.shape))
+    elif opts.render:
+        try:
+            dataset.set_view_source(MeshViewSource(dataset))
+        except FileNotFoundError as e:
+            raise SystemExit('--render: %s' % e)
     else:
-        raise SystemExit('rendering is out of scope: pass --views <file.npy> or --synthetic')
+        raise SystemExit('no views to embed: pass --render, --views <file.npy> or --synthetic')
 
 
 def _step_of(path):

@@ -16,7 +16,10 @@ static int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define AAE_HIP_TRY(expr)                                                                       \
+// for the library's other translation units (aae_render.hip): aae_last_error() reads the text of this one
+void set_last_error(const char* msg) { g_last_error = msg; }
+
+#define AAE_HIP_TRY(expr)                                                                      \
     do {                                                                                        \
         hipError_t e__ = (expr);                                                                \
         if (e__ != hipSuccess)                                                                  \

@@ -1,0 +1,214 @@
+// Host side of the mesh rasteriser: the mesh handle, the workspace layout and the launch sequence behind aae_render_*
+// (include/aae_hip.h).  Part of aae_render.hip.
+#pragma once
+
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/aae_hip.h"
+#include "kernels/render_raster.h"
+
+namespace aae_host {
+void set_last_error(const char* msg);          // aae_host_types.h: the thread's aae_last_error() text lives in aae_hip.hip
+}
+
+struct aae_mesh {
+    float* verts = nullptr;
+    float* normals = nullptr;
+    float* colors = nullptr;
+    int32_t* faces = nullptr;
+    int V = 0, F = 0, model = 0;
+};
+
+namespace aae_render {
+
+static int rfail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    aae_host::set_last_error(buf);
+    return code;
+}
+
+#define AAE_RENDER_TRY(expr)                                                                                            \
+    do {                                                                                                                \
+        hipError_t e__ = (expr);                                                                                        \
+        if (e__ != hipSuccess)                                                                                          \
+            return aae_render::rfail(AAE_ERR_RUNTIME, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+
+static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+struct WsLayout {
+    size_t rect, vtx, vary, keys, total;
+};
+
+static WsLayout ws_layout(int V, int n, int W, int H) {
+    WsLayout l;
+    size_t o = 0;
+    l.rect = o; o += up256((size_t)n * 4 * sizeof(int32_t));
+    l.vtx = o;  o += up256((size_t)n * V * sizeof(RcVertex));
+    l.vary = o; o += up256((size_t)n * V * RC_VARY * sizeof(float));
+    l.keys = o; o += up256((size_t)n * W * H * sizeof(unsigned long long));
+    l.total = o;
+    return l;
+}
+
+#define AAE_RENDER_MAX_DIM 4096
+#define AAE_RENDER_MAX_VIEWS 65535           /* the view is blockIdx.y */
+
+// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, int crop,
+                      void* crops_out, void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes,
+                      void* stream_, float* kernel_ms, const char* who) {
+    if (!m || !Rs || !p || !bbs_out || !visible_out || !ws) return rfail(AAE_ERR_INVALID, "%s: null argument", who);
+    if (n < 1 || n > AAE_RENDER_MAX_VIEWS) return rfail(AAE_ERR_UNSUPPORTED, "%s: %d views outside [1,%d] per call", who, n, AAE_RENDER_MAX_VIEWS);
+    if (p->W < 1 || p->H < 1 || p->W > AAE_RENDER_MAX_DIM || p->H > AAE_RENDER_MAX_DIM)
+        return rfail(AAE_ERR_UNSUPPORTED, "%s: render dims %dx%d outside [1,%d]", who, p->W, p->H, AAE_RENDER_MAX_DIM);
+    if (p->K[3] != 0.0 || p->K[6] != 0.0 || p->K[7] != 0.0)
+        return rfail(AAE_ERR_INVALID, "%s: K[1,0], K[2,0] and K[2,1] must be 0", who);
+    if (!(p->clip_near > 0.0) || !(p->clip_far > p->clip_near)) return rfail(AAE_ERR_INVALID, "%s: need 0 < near < far", who);
+    if (crops_out && (crop < 1 || crop > AAE_RENDER_MAX_DIM)) return rfail(AAE_ERR_UNSUPPORTED, "%s: crop size %d outside [1,%d]", who, crop, AAE_RENDER_MAX_DIM);
+    const WsLayout l = ws_layout(m->V, n, p->W, p->H);
+    if (ws_bytes < l.total) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    if (((uintptr_t)ws & 255) != 0) return rfail(AAE_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+
+    hipStream_t stream = (hipStream_t)stream_;
+    char* base = (char*)ws;
+    RenderArgs a;
+    a.verts = m->verts; a.normals = m->normals; a.colors = m->colors; a.faces = m->faces;
+    a.V = m->V; a.F = m->F;
+    a.Rs = Rs; a.ts = ts;
+    a.t[0] = p->t[0]; a.t[1] = p->t[1]; a.t[2] = p->t[2];
+    a.cam.K00 = p->K[0]; a.cam.K01 = p->K[1]; a.cam.K02 = p->K[2]; a.cam.K11 = p->K[4]; a.cam.K12 = p->K[5];
+    a.cam.near_ = p->clip_near; a.cam.far_ = p->clip_far;
+    a.cam.W = p->W; a.cam.H = p->H;
+    a.light.pos[0] = p->light[0]; a.light.pos[1] = p->light[1]; a.light.pos[2] = p->light[2];
+    a.light.ambient = p->ambient; a.light.diffuse = p->diffuse; a.light.specular = p->specular;
+    a.n = n;
+    a.rect = (int32_t*)(base + l.rect);
+    a.vtx = (RcVertex*)(base + l.vtx);
+    a.vary = (float*)(base + l.vary);
+    a.keys = (unsigned long long*)(base + l.keys);
+
+    hipEvent_t ev[7] = {};
+    if (kernel_ms)
+        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
+    int stage = 0;
+#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
+    const bool cad = m->model == AAE_MODEL_CAD;
+    const dim3 block(RENDER_BLOCK);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_init_rect, dim3((n + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    const dim3 vgrid((m->V + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
+    if (cad) AAE_LAUNCH(render_vertex<true>, vgrid, block, 0, stream, a);
+    else AAE_LAUNCH(render_vertex<false>, vgrid, block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_clear, dim3(RENDER_CLEAR_BLOCKS, n), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_raster, dim3((m->F + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_bbox, dim3(n), block, 0, stream, a, bbs_out, visible_out);
+    AAE_RENDER_MARK();
+    if (crops_out) {
+        const dim3 cgrid((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
+        if (cad) AAE_LAUNCH(render_crop<true>, cgrid, block, 0, stream, a, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)crops_out);
+        else AAE_LAUNCH(render_crop<false>, cgrid, block, 0, stream, a, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)crops_out);
+    } else {
+        const dim3 fgrid((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
+        if (cad) AAE_LAUNCH(render_frame<true>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
+        else AAE_LAUNCH(render_frame<false>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
+    }
+    AAE_RENDER_MARK();
+#undef AAE_RENDER_MARK
+    AAE_RENDER_TRY(hipGetLastError());
+    if (kernel_ms) {
+        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
+        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
+        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
+    }
+    return AAE_OK;
+}
+
+}  // namespace aae_render
+
+extern "C" {
+
+int aae_mesh_create(const float* verts, const float* normals, const float* colors, int n_verts, const int32_t* faces, int n_faces,
+                    int model, float vertex_scale, aae_mesh** out) {
+    using namespace aae_render;
+    if (!verts || !normals || !faces || !out) return rfail(AAE_ERR_INVALID, "aae_mesh_create: null argument");
+    if (n_verts < 1 || n_faces < 1) return rfail(AAE_ERR_INVALID, "aae_mesh_create: %d vertices, %d faces", n_verts, n_faces);
+    if (model != AAE_MODEL_RECONST && model != AAE_MODEL_CAD) return rfail(AAE_ERR_UNSUPPORTED, "aae_mesh_create: unknown model kind %d", model);
+    for (size_t i = 0; i < (size_t)n_faces * 3; ++i)
+        if (faces[i] < 0 || faces[i] >= n_verts)
+            return rfail(AAE_ERR_INVALID, "aae_mesh_create: face %zu names vertex %d of %d", i / 3, faces[i], n_verts);
+    const size_t nv3 = (size_t)n_verts * 3;
+    std::vector<float> scaled(nv3), col(nv3);
+    for (size_t i = 0; i < nv3; ++i) {
+        scaled[i] = verts[i] * vertex_scale;                                  // meshrenderer_phong.py:52-55: float32
+        col[i] = colors ? colors[i] : 160.0f / 255.0f;                         // meshrenderer_phong.py:50
+    }
+    aae_mesh* m = new aae_mesh();
+    m->V = n_verts; m->F = n_faces; m->model = model;
+    hipError_t e = hipMalloc((void**)&m->verts, nv3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->normals, nv3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->colors, nv3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->faces, (size_t)n_faces * 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(m->verts, scaled.data(), nv3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->normals, normals, nv3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->colors, col.data(), nv3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->faces, faces, (size_t)n_faces * 3 * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        aae_mesh_destroy(m);
+        return rfail(AAE_ERR_RUNTIME, "aae_mesh_create: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return AAE_OK;
+}
+
+void aae_mesh_destroy(aae_mesh* m) {
+    if (!m) return;
+    if (m->verts) (void)hipFree(m->verts);
+    if (m->normals) (void)hipFree(m->normals);
+    if (m->colors) (void)hipFree(m->colors);
+    if (m->faces) (void)hipFree(m->faces);
+    delete m;
+}
+
+size_t aae_render_workspace_bytes(const aae_mesh* mesh, int n_views, int W, int H) {
+    if (!mesh || n_views < 1 || W < 1 || H < 1) return 0;
+    return aae_render::ws_layout(mesh->V, n_views, W, H).total;
+}
+
+int aae_render_embedding_views(const aae_mesh* mesh, const double* Rs, int n, const aae_render_params* params, int crop,
+                               void* crops_out, int32_t* bbs_out, int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream) {
+    if (!crops_out) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_embedding_views: null argument");
+    return aae_render::render_run(mesh, Rs, nullptr, n, params, crop, crops_out, nullptr, nullptr, nullptr, bbs_out, visible_out, workspace, ws_bytes,
+                                  stream, nullptr, "aae_render_embedding_views");
+}
+
+int aae_render_embedding_views_timed(const aae_mesh* mesh, const double* Rs, int n, const aae_render_params* params, int crop,
+                                     void* crops_out, int32_t* bbs_out, int32_t* visible_out, void* workspace, size_t ws_bytes,
+                                     void* stream, float* kernel_ms) {
+    if (!crops_out || !kernel_ms) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_embedding_views_timed: null argument");
+    return aae_render::render_run(mesh, Rs, nullptr, n, params, crop, crops_out, nullptr, nullptr, nullptr, bbs_out, visible_out, workspace, ws_bytes,
+                                  stream, kernel_ms, "aae_render_embedding_views_timed");
+}
+
+int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, int n, const aae_render_params* params,
+                      void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* workspace,
+                      size_t ws_bytes, void* stream) {
+    if (!bgr_out || !depth_out) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_frames: null argument");
+    return aae_render::render_run(mesh, Rs, ts, n, params, 0, nullptr, bgr_out, depth_out, tri_out, bbs_out, visible_out, workspace, ws_bytes,
+                                  stream, nullptr, "aae_render_frames");
+}
+
+}  // extern "C"

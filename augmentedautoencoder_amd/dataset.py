@@ -3,11 +3,14 @@ inference hot path touches: the cfg keyword bag, the crop shape, the
 codebook-row -> rotation table, and the hook through which update_embedding
 obtains the views to embed.
 
-Rendering (OpenGL meshrenderer), augmentation and training-set generation are
-out of scope: ``render_embedding_image_batch``
-delegates to a pluggable *view source* instead of an OpenGL context.
+Augmentation and training-set generation are out of scope (SURVEY.md section 2,
+rows 5 and 10).  ``render_embedding_image_batch`` delegates to a pluggable *view
+source*; ``MeshViewSource`` is the one that renders the object's mesh on the GPU
+(meshrenderer.py, the HIP rasteriser) in place of the reference's OpenGL context.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -81,6 +84,45 @@ def vs_calc_2d_bbox(xs, ys, im_size):
     return [tl[0], tl[1], br[0] - tl[0], br[1] - tl[1]]
 
 
+class MeshViewSource(object):
+    """The view source that does what dataset.py:308-352 does: render codebook rows [start,end) of the dataset's mesh
+    (Renderer.render at t = (0, 0, RADIUS)), take calc_2d_bbox of the depth, and cut the padded square patch resized with
+    INTER_NEAREST -- on the GPU, for the whole batch in one call.  Returns (uint8 device tensor [n,H,W,3] BGR, numpy obj_bbs
+    [n,4]); Codebook.update_embedding feeds the tensor to the encoder as it is, the views never visit the host.
+    Raises ValueError naming the first row whose view covers no pixel (the reference's ValueError from calc_2d_bbox on an
+    empty selection, dataset.py:273-277 -- 'Have you scaled the vertices to mm?')."""
+
+    def __init__(self, dataset):
+        from .codebook import _parse_K
+        kw = dataset._kw
+        h, w, c = dataset.shape
+        if c != 3:
+            raise NotImplementedError('C = %d: the grey-scale conversion (cv2.cvtColor, dataset.py:349-350) is not implemented; use C = 3' % c)
+        if h != w:
+            raise NotImplementedError('H = %d, W = %d: only square crops (the reference hands shape[:2] to cv2.resize as (width, height), '
+                                      'dataset.py:347, and is only right for squares)' % (h, w))
+        self.dataset = dataset
+        self.crop = int(h)
+        self.renderer = dataset.renderer
+        dims = _parse_K(kw['render_dims'])
+        if not isinstance(dims, list) or len(dims) != 2:
+            raise ValueError('[Dataset] RENDER_DIMS must be (width, height), got %r' % (kw['render_dims'],))
+        self.render_dims = (int(dims[0]), int(dims[1]))
+        self.K = np.array(_parse_K(kw['k']), dtype=np.float64).reshape(3, 3)
+        self.clip_near = float(kw['clip_near'])
+        self.clip_far = float(kw['clip_far'])
+        self.pad_factor = float(kw['pad_factor'])
+        self.t = np.array([0, 0, float(kw['radius'])])
+
+    def __call__(self, start, end, Rs):
+        crops, bbs, visible = self.renderer.render_embedding_views(0, self.render_dims[0], self.render_dims[1], self.K, Rs, self.t,
+                                                                   self.clip_near, self.clip_far, self.pad_factor, self.crop)
+        hidden = np.nonzero(visible.cpu().numpy() == 0)[0]
+        if len(hidden):
+            raise ValueError('Object in Rendering not visible (codebook row %d). Have you scaled the vertices to mm?' % (start + int(hidden[0])))
+        return crops, bbs.cpu().numpy().astype(np.float64)
+
+
 class Dataset(object):
 
     def __init__(self, dataset_path, **kw):
@@ -100,6 +142,20 @@ class Dataset(object):
         if key not in _VIEWSPHERE_CACHE:
             _VIEWSPHERE_CACHE[key] = vs.viewsphere_for_embedding(*key)
         return _VIEWSPHERE_CACHE[key]
+
+    @lazy_property
+    def renderer(self):
+        """dataset.py:60-80: the renderer of [Dataset] MODEL / MODEL_PATH / ANTIALIASING / VERTEX_SCALE (here VERTEX_SCALE
+        scales both kinds of model; the reference's reconst call hands it to the unused ``clamp`` parameter)."""
+        from . import meshrenderer
+        kw = self._kw
+        kind = kw.get('model')
+        if kind not in meshrenderer.MODEL_KINDS:
+            raise ValueError("[Dataset] MODEL must be 'cad' or 'reconst', got %r" % (kind,))
+        path = kw.get('model_path')
+        if not path or not os.path.isfile(path):
+            raise FileNotFoundError('[Paths] MODEL_PATH: no such file: %s' % (path,))
+        return meshrenderer.Renderer([path], int(kw.get('antialiasing', 1)), self.dataset_path, float(kw.get('vertex_scale', 1.0)), model=kind)
 
     @property
     def embedding_size(self):

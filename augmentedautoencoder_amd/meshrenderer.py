@@ -1,0 +1,307 @@
+"""``Renderer`` with the signature of the reference's two OpenGL renderers
+(/root/reference/auto_pose/meshrenderer/meshrenderer_phong.py for ``model='reconst'``, meshrenderer.py for
+``model='cad'``), backed by the HIP software rasteriser of libaae_hip.so (csrc/kernels/render_core.h states what is
+computed and how exactly), plus the PLY reader the reference loads its models with.
+
+No OpenGL, EGL or pyassimp: the mesh is uploaded once (``aae_mesh_create``) and every call renders a batch of views
+in six launches.  Parity with a real OpenGL driver is unpinned; the geometry is reproducible bit for bit against the
+float64 restatement of the tests."""
+from __future__ import annotations
+
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _lib
+
+MODEL_KINDS = {'reconst': _lib.AAE_MODEL_RECONST, 'cad': _lib.AAE_MODEL_CAD}
+DEFAULT_LIGHT = (400., 400., 400.)                                   # meshrenderer_phong.py:126
+DEFAULT_PHONG = {'ambient': 0.4, 'diffuse': 0.8, 'specular': 0.3}    # meshrenderer_phong.py:101
+
+_PLY_FORMATS = {'float': ('f', 4), 'double': ('d', 8), 'int': ('i', 4), 'uchar': ('B', 1)}      # inout.py:82-87
+
+
+def load_ply(path):
+    """gl_utils/inout.py:8-155: ``pts`` [n,3], and where the file has them ``normals`` [n,3], ``colors`` [n,3],
+    ``texture_uv`` [n,2] and ``faces`` [m,3], all float64 as the reference returns them; ascii and
+    binary_little_endian; only the scalar types of inout.py:82-87 and triangular faces."""
+    with open(path, 'rb') as f:
+        n_pts = n_faces = 0
+        pt_props, face_props = [], []
+        is_binary = False
+        section = None
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise ValueError('%s: no end_header' % path)
+            line = raw.decode('ascii', 'replace').rstrip('\n').rstrip('\r')
+            if line.startswith('element vertex'):
+                n_pts = int(line.split()[-1])
+                section = 'vertex'
+            elif line.startswith('element face'):
+                n_faces = int(line.split()[-1])
+                section = 'face'
+            elif line.startswith('element'):
+                section = None
+            elif line.startswith('property') and section == 'vertex':
+                pt_props.append((line.split()[-1], line.split()[-2]))
+            elif line.startswith('property list') and section == 'face':
+                elems = line.split()
+                if elems[-1] == 'vertex_indices':
+                    face_props.append(('n_corners', elems[2]))
+                    face_props += [('ind_%d' % i, elems[3]) for i in range(3)]
+            elif line.startswith('format'):
+                if 'binary_big_endian' in line:
+                    raise ValueError('%s: binary_big_endian PLY is not supported' % path)
+                is_binary = 'binary' in line
+            elif line.startswith('end_header'):
+                break
+        names = [p[0] for p in pt_props]
+        model = {'pts': np.zeros((n_pts, 3), np.float64)}
+        if n_faces > 0:
+            model['faces'] = np.zeros((n_faces, 3), np.float64)
+        groups = [('pts', ('x', 'y', 'z'))]
+        if {'nx', 'ny', 'nz'}.issubset(names):
+            model['normals'] = np.zeros((n_pts, 3), np.float64)
+            groups.append(('normals', ('nx', 'ny', 'nz')))
+        if {'red', 'green', 'blue'}.issubset(names):
+            model['colors'] = np.zeros((n_pts, 3), np.float64)
+            groups.append(('colors', ('red', 'green', 'blue')))
+        if {'texture_u', 'texture_v'}.issubset(names):
+            model['texture_uv'] = np.zeros((n_pts, 2), np.float64)
+            groups.append(('texture_uv', ('texture_u', 'texture_v')))
+        for kind in [p[1] for p in pt_props + face_props]:
+            if is_binary and kind not in _PLY_FORMATS:
+                raise ValueError('%s: property type %r is not supported' % (path, kind))
+
+        if is_binary:
+            vfmt = '<' + ''.join(_PLY_FORMATS[p[1]][0] for p in pt_props)
+            vsize = struct.calcsize(vfmt)
+            rows = [struct.unpack(vfmt, f.read(vsize)) for _ in range(n_pts)]
+        else:
+            rows = [f.readline().decode('ascii').split() for _ in range(n_pts)]
+        col = {name: k for k, name in enumerate(names)}
+        for key, props in groups:
+            for j, prop in enumerate(props):
+                model[key][:, j] = [float(r[col[prop]]) for r in rows]
+
+        if n_faces > 0:
+            if is_binary:
+                ffmt = '<' + ''.join(_PLY_FORMATS[p[1]][0] for p in face_props)
+                fsize = struct.calcsize(ffmt)
+                frows = [struct.unpack(ffmt, f.read(fsize)) for _ in range(n_faces)]
+            else:
+                frows = [f.readline().decode('ascii').split() for _ in range(n_faces)]
+            fcol = {p[0]: k for k, p in enumerate(face_props)}
+            for i, r in enumerate(frows):
+                if int(r[fcol['n_corners']]) != 3:
+                    raise ValueError('%s: only triangular faces are supported (face %d has %d corners)' % (path, i, int(r[fcol['n_corners']])))
+                model['faces'][i] = [int(r[fcol['ind_0']]), int(r[fcol['ind_1']]), int(r[fcol['ind_2']])]
+    return model
+
+
+def calc_normals(vertices):
+    """gl_utils/geometry.py:67-80 for a whole triangle soup at once: the face normal, repeated for its three vertices,
+    zero for a zero-area face; float32 arithmetic as the reference's float32 vertices give it."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3, 3)
+    normal = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    norm = np.sqrt((normal * normal).sum(axis=1, dtype=np.float32))
+    safe = np.where(norm == 0, np.float32(1), norm)
+    normal = np.where((norm == 0)[:, None], np.float32(0), normal / safe[:, None]).astype(np.float32)
+    return np.repeat(normal, 3, axis=0)
+
+
+def mesh_arrays(model, kind):
+    """The vertex buffer of a loaded model: (verts f32 [V,3] unscaled, normals f32 [V,3], colors f32 [V,3] rgb in [0,1],
+    faces int32 [F,3]).  reconst: load_meshes_sixd + meshrenderer_phong.py:41-55 (indexed, the file's normals, colours
+    through uint32, 160 without).  cad: meshrenderer.py:37-42, a non-indexed triangle soup with recalculated per-face
+    normals (the reference reads it through pyassimp; here the soup is built from the PLY's faces)."""
+    if kind not in MODEL_KINDS:
+        raise ValueError("model must be 'reconst' or 'cad', got %r" % (kind,))
+    if 'faces' not in model:
+        raise ValueError('the model has no faces')
+    pts = np.asarray(model['pts']).astype(np.float32)
+    faces = np.asarray(model['faces']).astype(np.uint32).astype(np.int64)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(pts)):
+        raise ValueError('a face names vertex %d of %d' % (faces.max(), len(pts)))
+    if kind == 'cad':
+        verts = np.ascontiguousarray(pts[faces.reshape(-1)])
+        normals = calc_normals(verts)
+        colors = np.empty_like(verts)
+        colors[:] = np.array([223., 214., 205.], dtype=np.float32) / np.float32(255)
+        faces = np.arange(len(verts), dtype=np.int32).reshape(-1, 3)
+        return verts, normals, colors, faces
+    if 'normals' not in model:
+        raise ValueError("model='reconst' needs per-vertex normals in the PLY (nx, ny, nz)")
+    normals = np.asarray(model['normals']).astype(np.float32)
+    if 'colors' in model:
+        colors = (np.asarray(model['colors']).astype(np.uint32) / 255.0).astype(np.float32)
+    else:
+        colors = ((np.ones_like(pts) * 160.0) / 255.0).astype(np.float32)
+    return np.ascontiguousarray(pts), np.ascontiguousarray(normals), np.ascontiguousarray(colors), np.ascontiguousarray(faces.astype(np.int32))
+
+
+def draw_light(random_light, phong, kind):
+    """(light position, ambient, diffuse, specular) of one render call; random_light draws them with the reference's
+    np.random calls in the reference's order (meshrenderer_phong.py:117-129, meshrenderer.py:97-109)."""
+    phong = DEFAULT_PHONG if phong is None else phong
+    if not random_light:
+        return DEFAULT_LIGHT, phong['ambient'], phong['diffuse'], phong['specular']
+    light = 1000. * np.random.random(3)
+    ambient = phong['ambient'] + (0.1 * (2 * np.random.rand() - 1) if kind == 'cad' else 0.0)
+    diffuse = phong['diffuse'] + 0.1 * (2 * np.random.rand() - 1)
+    specular = phong['specular'] + 0.1 * (2 * np.random.rand() - 1)
+    return tuple(light), ambient, diffuse, specular
+
+
+def render_params(W, H, K, t, near, far, pad_factor=1.0, light=DEFAULT_LIGHT, ambient=0.4, diffuse=0.8, specular=0.3):
+    p = _lib.RenderParams()
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    p.K[:] = K.reshape(-1).tolist()
+    p.t[:] = np.asarray(t, dtype=np.float64).reshape(-1)[:3].tolist() if t is not None else [0.0, 0.0, 0.0]
+    p.W, p.H = int(W), int(H)
+    p.clip_near, p.clip_far, p.pad_factor = float(near), float(far), float(pad_factor)
+    p.light[:] = [float(v) for v in light]
+    p.ambient, p.diffuse, p.specular = float(ambient), float(diffuse), float(specular)
+    return p
+
+
+class Renderer(object):
+
+    MAX_FBO_WIDTH = 2000
+    MAX_FBO_HEIGHT = 2000
+
+    def __init__(self, models_cad_files, samples=1, vertex_tmp_store_folder='.', vertex_scale=1.0, model='reconst', device=None):
+        if int(samples) > 1:
+            raise NotImplementedError('ANTIALIASING = %d: multisampling is not implemented (the MSAA resolve is driver-defined); use 1' % int(samples))
+        if model not in MODEL_KINDS:
+            raise ValueError("model must be 'reconst' or 'cad', got %r" % (model,))
+        self.model = model
+        self.vertex_scale = float(vertex_scale)
+        self._samples = int(samples)
+        # a model is a PLY path or an already loaded dict (load_ply's keys); no vertex cache file: loading is not the cost here
+        self._arrays = [mesh_arrays(p if isinstance(p, dict) else load_ply(p), model) for p in models_cad_files]
+        self._device = device
+        self._meshes = None
+        self._ws = None
+        self.lib = None
+
+    # ---- device state, created at first use ---------------------------------------
+    def _open(self):
+        if self._meshes is not None:
+            return
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError('the mesh rasteriser needs the GPU (libaae_hip.so): there is no CPU fallback')
+        self.lib = _lib.load()
+        if self._device is None:
+            self._device = torch.device('cuda', torch.cuda.current_device())
+        meshes = []
+        with torch.cuda.device(self._device):
+            for verts, normals, colors, faces in self._arrays:
+                h = ctypes.c_void_p()
+                rc = self.lib.aae_mesh_create(verts.ctypes.data, normals.ctypes.data, colors.ctypes.data, len(verts), faces.ctypes.data, len(faces),
+                                              MODEL_KINDS[self.model], self.vertex_scale, ctypes.byref(h))
+                _lib.check(self.lib, rc, 'aae_mesh_create')
+                meshes.append(h)
+        self._meshes = meshes
+
+    def _workspace(self, mesh, n, W, H):
+        import torch
+        need = int(self.lib.aae_render_workspace_bytes(mesh, n, W, H))
+        if self._ws is None or self._ws.numel() - (-self._ws.data_ptr()) % 256 < need:
+            self._ws = None
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self._device)
+        return self._ws.data_ptr() + (-self._ws.data_ptr()) % 256, need
+
+    def _upload(self, a, cols):
+        import torch
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self._device, dtype=torch.float64).reshape(-1, cols).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, cols)), device=self._device)
+
+    def _stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+
+    # ---- rendering ------------------------------------------------------------------
+    def render_batch(self, obj_id, W, H, K, Rs, ts, near, far, random_light=False, phong=None, workspace=None, return_tri=False):
+        """n views in one call: Rs [n,3,3], ts [n,3] or one [3] for all -> (bgr uint8 [n,H,W,3], depth float32 [n,H,W],
+        obj_bbs int32 [n,4], visible int32 [n]) as device tensors, with return_tri=True also the index of the visible face
+        per pixel (int32 [n,H,W], -1 = background).  One light for the batch, as one render call has."""
+        import torch
+        self._open()
+        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
+        W, H = int(W), int(H)
+        mesh = self._meshes[obj_id]
+        Rd = self._upload(Rs, 9)
+        n = Rd.shape[0]
+        t_arr = np.asarray(ts.cpu() if isinstance(ts, torch.Tensor) else ts, dtype=np.float64)
+        td = None if t_arr.size == 3 else self._upload(t_arr, 3)
+        if td is not None and td.shape[0] != n:
+            raise ValueError('%d rotations, %d translations' % (n, td.shape[0]))
+        light, a, d, s = draw_light(random_light, phong, self.model)
+        p = render_params(W, H, K, t_arr if td is None else None, near, far, 1.0, light, a, d, s)
+        with torch.cuda.device(self._device):
+            bgr = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self._device)
+            depth = torch.empty((n, H, W), dtype=torch.float32, device=self._device)
+            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
+            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
+            tri = torch.empty((n, H, W), dtype=torch.int32, device=self._device) if return_tri else None
+            ws_ptr, ws_bytes = workspace if workspace is not None else self._workspace(mesh, n, W, H)
+            rc = self.lib.aae_render_frames(mesh, ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(td.data_ptr()) if td is not None else None, n,
+                                            ctypes.byref(p), ctypes.c_void_p(bgr.data_ptr()), ctypes.c_void_p(depth.data_ptr()),
+                                            ctypes.c_void_p(tri.data_ptr()) if return_tri else None, ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes,
+                                            self._stream())
+        _lib.check(self.lib, rc, 'aae_render_frames')
+        if return_tri:
+            return bgr, depth, bbs, vis, tri
+        return bgr, depth, bbs, vis
+
+    def render_embedding_views(self, obj_id, W, H, K, Rs, t, near, far, pad_factor, crop, random_light=False, phong=None, workspace=None,
+                               timed=False):
+        """Renderer.render + calc_2d_bbox + extract_square_patch(INTER_NEAREST) of dataset.py:326-347 for n rotations at one
+        translation: (crops uint8 [n,crop,crop,3] BGR, obj_bbs int32 [n,4], visible int32 [n]) as device tensors; with
+        timed=True also the milliseconds of the six launches."""
+        import torch
+        self._open()
+        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
+        W, H, crop = int(W), int(H), int(crop)
+        mesh = self._meshes[obj_id]
+        Rd = self._upload(Rs, 9)
+        n = Rd.shape[0]
+        light, a, d, s = draw_light(random_light, phong, self.model)
+        p = render_params(W, H, K, t, near, far, pad_factor, light, a, d, s)
+        with torch.cuda.device(self._device):
+            crops = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
+            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
+            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
+            ws_ptr, ws_bytes = workspace if workspace is not None else self._workspace(mesh, n, W, H)
+            args = (mesh, ctypes.c_void_p(Rd.data_ptr()), n, ctypes.byref(p), crop, ctypes.c_void_p(crops.data_ptr()), ctypes.c_void_p(bbs.data_ptr()),
+                    ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
+            if timed:
+                ms = (ctypes.c_float * 6)()
+                _lib.check(self.lib, self.lib.aae_render_embedding_views_timed(*(args + (ms,))), 'aae_render_embedding_views_timed')
+                return crops, bbs, vis, list(ms)
+            _lib.check(self.lib, self.lib.aae_render_embedding_views(*args), 'aae_render_embedding_views')
+        return crops, bbs, vis
+
+    def render(self, obj_id, W, H, K, R, t, near, far, random_light=False, phong=None):
+        """meshrenderer_phong.py:101-168 / meshrenderer.py:84-137: (bgr uint8 [H,W,3], depth float32 [H,W]) on the host."""
+        bgr, depth, _, _ = self.render_batch(obj_id, W, H, K, np.asarray(R, dtype=np.float64).reshape(1, 3, 3),
+                                             np.asarray(t, dtype=np.float64).reshape(3), near, far, random_light, phong)
+        return bgr[0].cpu().numpy(), depth[0].cpu().numpy()
+
+    def close(self):
+        if self._meshes is not None:
+            for h in self._meshes:
+                self.lib.aae_mesh_destroy(h)
+        self._meshes = None
+        self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

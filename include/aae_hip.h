@@ -344,6 +344,55 @@ double aae_decoder_kernel_flops(const aae_decoder* dec, int i);
 /* workspace region of hidden activation `stage` (0 = dense output, i = i-th hidden conv) */
 int aae_decoder_activation_info(const aae_decoder* dec, int B, int stage, size_t* offset_bytes, size_t* count);
 
+/* ---- Mesh rasteriser: the views a codebook is built from -----------------------------------------
+ * Replaces Renderer.render (auto_pose/meshrenderer/meshrenderer_phong.py:101-168 for model = reconst,
+ * meshrenderer.py:84-137 for model = cad: one OpenGL draw per view), calc_2d_bbox on the rendered depth
+ * (pysixd/view_sampler.py:10-15) and extract_square_patch + cv2.resize(INTER_NEAREST) on the rendered colour
+ * (auto_pose/ae/dataset.py:308-373) for a batch of views in a few launches.  Geometry is float64 / integer and
+ * reproducible bit for bit (csrc/kernels/render_core.h states the rule); parity with an OpenGL driver is unpinned.
+ * Deviations: a triangle with a vertex nearer than `near` is dropped whole instead of clipped; no multisampling. */
+typedef struct aae_mesh aae_mesh;
+
+#define AAE_MODEL_RECONST 0       /* indexed mesh, per-vertex normals and colours, Phong shader                */
+#define AAE_MODEL_CAD 1           /* triangle soup with per-face normals, constant material (cad_shader.frag)  */
+
+/* Host arrays, copied to the device: verts / normals [n_verts,3] float32, colors [n_verts,3] float32 rgb in [0,1] or NULL
+ * (160/255, meshrenderer_phong.py:50), faces [n_faces,3] int32 (every index is checked).  Vertices are stored as
+ * float32(vertex * vertex_scale), as the reference's vertex buffer holds them. */
+int aae_mesh_create(const float* verts, const float* normals, const float* colors, int n_verts, const int32_t* faces, int n_faces,
+                    int model, float vertex_scale, aae_mesh** out);
+void aae_mesh_destroy(aae_mesh* mesh);
+
+typedef struct aae_render_params {
+    double K[9];                  /* row-major intrinsics; K[3], K[6], K[7] must be 0 (camera.py:177-185)      */
+    double t[3];                  /* translation of every view when the call takes no per-view ts            */
+    int32_t W, H;                 /* render dims                                                               */
+    double clip_near, clip_far;
+    double pad_factor;            /* [Dataset] PAD_FACTOR (embedding views only)                               */
+    float light[3];               /* light position in eye coordinates; the reference's default (400,400,400) */
+    float ambient, diffuse, specular;   /* 0.4, 0.8, 0.3                                                       */
+} aae_render_params;
+
+size_t aae_render_workspace_bytes(const aae_mesh* mesh, int n_views, int W, int H);
+
+/* Dataset.render_embedding_image_batch without the host: Rs device float64 [n,9] (row-major rotations) ->
+ * crops_out device uint8 [n,crop,crop,3] BGR, bbs_out device int32 [n,4] (x, y, w, h), visible_out device int32 [n]
+ * (0: no pixel covered -- the reference raises ValueError from calc_2d_bbox; that view's crop and box are 0).
+ * The workspace may hold anything on entry; no allocation, no synchronisation, capturable into a graph.  n <= 65535. */
+int aae_render_embedding_views(const aae_mesh* mesh, const double* Rs, int n, const aae_render_params* params, int crop,
+                               void* crops_out, int32_t* bbs_out, int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream);
+/* the same call with the time of each of its six launches (init, vertex, clear, raster, bbox, crop) from events on
+ * `stream`; synchronises, so not for capture */
+int aae_render_embedding_views_timed(const aae_mesh* mesh, const double* Rs, int n, const aae_render_params* params, int crop,
+                                     void* crops_out, int32_t* bbs_out, int32_t* visible_out, void* workspace, size_t ws_bytes,
+                                     void* stream, float* kernel_ms);
+/* Full frames: ts device float64 [n,3] (one translation per view) or NULL (params->t) -> bgr_out device uint8 [n,H,W,3],
+ * depth_out device float32 [n,H,W] (0 = background), tri_out device int32 [n,H,W] or NULL (index of the visible face, -1 =
+ * background), bbs_out / visible_out as above. */
+int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, int n, const aae_render_params* params,
+                      void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* workspace,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
