@@ -174,88 +174,25 @@ void aae_encoder_destroy(aae_encoder* enc) {
     delete enc;
 }
 
+// The value rules of the options, and the product build's gate, are rows of kOptionTable (aae_options.h: apply_option).  In front
+// of them: what needs the handle or the runtime.
 int aae_encoder_set_option(aae_encoder* enc, const char* name, int value) {
     using namespace aae_host;
     if (!enc || !name) return fail(AAE_ERR_INVALID, "aae_encoder_set_option: null argument");
-#ifndef AAE_EXPERIMENTS
-    {
-        // Kernel variants that measured slower than the defaults, and the profiling / ablation aids (one of which makes results wrong
-        // on purpose), are compiled into the experiments build only (-DAAE_EXPERIMENTS: libaae_hip_experiments.so, tools/ and the A/B
-        // tests).  Here their options accept the default value and nothing else.
-        static const struct { const char* name; int only; } kExperimentOptions[] = {
-            {"detect_chain", 0}, {"chain_timeline", 0}, {"wavek_timeline", 0}, {"wavek_ablate", 0}, {"wavek_waves", 4}, {"wavek_tiny_waves", 4},
-            {"wavek_depth", 2}, {"wavek_pingpong", 0}, {"gemv_ticket", 1}, {"wavek_spread", 3}, {"igemm_dma", 1}, {"igemm_breg", 1}, {"x3h_dma", 1}, {"x3h_wide_min_blocks", 0}, {"winograd_wide", 0}};
-        for (const auto& o : kExperimentOptions)
-            if (!strcmp(name, o.name)) {
-                if (value == o.only) return AAE_OK;
-                return fail(AAE_ERR_UNSUPPORTED, "option '%s' = %d selects a kernel variant / profiling aid of the experiments build (-DAAE_EXPERIMENTS); this build runs '%s' = %d",
-                            name, value, name, o.only);
-            }
-        if (!strcmp(name, "detect_chain_blocks")) return AAE_OK;
-    }
-#endif
-    if (!strcmp(name, "splitk_min_base_blocks")) enc->splitk_min_base_blocks = value;
-    else if (!strcmp(name, "splitk_target_blocks")) enc->splitk_target_blocks = value;
-    else if (!strcmp(name, "reduce_small")) enc->reduce_small = value ? 1 : 0;
-    else if (!strcmp(name, "igemm_stagger")) enc->igemm_stagger = value;
-    else if (!strcmp(name, "x3h_dma")) enc->x3h_dma = value ? 1 : 0;
-    else if (!strcmp(name, "x3h_wide256")) enc->x3h_wide256 = value ? 1 : 0;
-    else if (!strcmp(name, "x3h_min_tiles")) enc->x3h_min_tiles = value < 0 ? 0 : value;
-    else if (!strcmp(name, "x3h_wide256_min_blocks")) enc->x3h_wide256_min_blocks = value < 1 ? 1 : value;
-    else if (!strcmp(name, "x3h_wide_min_blocks")) enc->x3h_wide_min_blocks = value < 0 ? 0 : value;
-    else if (!strcmp(name, "igemm_dma")) enc->igemm_dma = value ? 1 : 0;
-    else if (!strcmp(name, "igemm_breg")) enc->igemm_breg = value ? 1 : 0;
-    else if (!strcmp(name, "dense_gemv")) enc->dense_gemv = value ? 1 : 0;
-    else if (!strcmp(name, "dense_gemv_max_batch")) enc->dense_gemv_max_batch = value;
-    else if (!strcmp(name, "wavek_tail_split")) enc->wavek_tail_split = value ? 1 : 0;
-    else if (!strcmp(name, "planner_cost_min_batch")) enc->planner_cost_min_batch = value < 1 ? 1 : value;
-    else if (!strcmp(name, "planner_cost_batch3")) enc->planner_cost_batch3 = value ? 1 : 0;
-    else if (!strcmp(name, "wavek_eff64x32_pct")) enc->wavek_eff64x32_pct = value < 30 ? 30 : (value > 100 ? 100 : value);
-    else if (!strcmp(name, "wavek_g_boost")) enc->wavek_g_boost = value < 1 ? 1 : (value > 4 ? 4 : value);
-    else if (!strcmp(name, "wavek_force_tail_tiles")) enc->wavek_force_tail_tiles = value < 0 ? 0 : value;
-    else if (!strcmp(name, "wavek_force_tail_g")) enc->wavek_force_tail_g = value < 2 ? 2 : value;
-    else if (!strcmp(name, "gemv_ticket")) enc->gemv_ticket = value ? 1 : 0;
-    else if (!strcmp(name, "wavek")) enc->wavek = value ? 1 : 0;
-    else if (!strcmp(name, "wavek_dense")) enc->wavek_dense = value ? 1 : 0;
-    else if (!strcmp(name, "wavek_ablate")) enc->wavek_ablate = value;
-    else if (!strcmp(name, "wavek_balance")) enc->wavek_balance = value ? 1 : 0;
-    else if (!strcmp(name, "planner_cost_model")) enc->planner_cost_model = value ? 1 : 0;
-    else if (!strcmp(name, "ticket_prep")) enc->ticket_prep = value ? 1 : 0;
-    else if (!strcmp(name, "multi_group_plan")) enc->multi_group_plan = value ? 1 : 0;
-    else if (!strcmp(name, "multi_xcd_affine")) enc->multi_xcd_affine = value ? 1 : 0;
-    else if (!strcmp(name, "multi_force_depth")) enc->multi_force_depth = value;
-    else if (!strcmp(name, "multi_force_shape")) enc->multi_force_shape = value;
-    else if (!strcmp(name, "multi_force_g")) enc->multi_force_g = value;
 #ifdef AAE_EXPERIMENTS
-    else if (!strcmp(name, "detect_chain")) {
-        if (value) {
-            // the persistent launch's grid barrier needs EVERY block resident: refuse the option unless the runtime confirms that one
-            // 256-thread block with the chain's LDS footprint fits a compute unit and the device's CU count is known (a plain launch
-            // of an over-sized grid would spin until its bounded wait traps).  A CU mask smaller than the device is not detectable
-            // from here: the option stays opt-in.
-            if (enc->cu_count <= 0) return fail(AAE_ERR_UNSUPPORTED, "detect_chain: the device's compute-unit count is unknown");
-            int per_cu = 0;
-            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)aae::detect_chain_kernel<1, 0, 0, 0>, 256, aae::kChainSmem);
-            if (e != hipSuccess || per_cu < 1)
-                return fail(AAE_ERR_UNSUPPORTED, "detect_chain: the runtime does not confirm residency of the persistent launch (%s, %d blocks per CU)",
-                            e == hipSuccess ? "ok" : hipGetErrorString(e), per_cu);
-        }
-        enc->detect_chain = value ? 1 : 0;
+    if (!strcmp(name, "detect_chain") && value) {
+        // the persistent launch's grid barrier needs EVERY block resident: refuse the option unless the runtime confirms that one
+        // 256-thread block with the chain's LDS footprint fits a compute unit and the device's CU count is known (a plain launch
+        // of an over-sized grid would spin until its bounded wait traps).  A CU mask smaller than the device is not detectable
+        // from here: the option stays opt-in.
+        if (enc->cu_count <= 0) return fail(AAE_ERR_UNSUPPORTED, "detect_chain: the device's compute-unit count is unknown");
+        int per_cu = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)aae::detect_chain_kernel<1, 0, 0, 0>, 256, aae::kChainSmem);
+        if (e != hipSuccess || per_cu < 1)
+            return fail(AAE_ERR_UNSUPPORTED, "detect_chain: the runtime does not confirm residency of the persistent launch (%s, %d blocks per CU)",
+                        e == hipSuccess ? "ok" : hipGetErrorString(e), per_cu);
     }
-#endif
-    else if (!strcmp(name, "detect_chain_blocks")) enc->detect_chain_blocks = value < 1 ? 1 : (value > aae_host::kChainMaxBlocks ? aae_host::kChainMaxBlocks : value);
-    else if (!strcmp(name, "compact_workspace")) enc->compact_workspace = value ? 1 : 0;
-    else if (!strcmp(name, "chain_timeline")) {
-        if (value && !enc->wavek_timeline) {
-            void* p = nullptr;
-            AAE_HIP_TRY(hipMalloc(&p, 3 * 512 * 8 * sizeof(long long)));
-            enc->allocations.push_back(p);
-            enc->wavek_timeline = static_cast<long long*>(p);
-        }
-        enc->chain_timeline = value < 0 ? 0 : value;           // 1: phase edges of the launch; 1 + l: also the inner stamps of conv layer l (2 = conv2 ...)
-        if (!value) enc->wavek_timeline = nullptr;
-    }
-    else if (!strcmp(name, "wavek_timeline")) {
+    if (!strcmp(name, "chain_timeline") || !strcmp(name, "wavek_timeline")) {
         if (value && !enc->wavek_timeline) {
             void* p = nullptr;
             AAE_HIP_TRY(hipMalloc(&p, 3 * 512 * 8 * sizeof(long long)));
@@ -264,79 +201,25 @@ int aae_encoder_set_option(aae_encoder* enc, const char* name, int value) {
         }
         if (!value) enc->wavek_timeline = nullptr;     // (the buffer stays in `allocations` until the handle goes)
     }
-    else if (!strcmp(name, "wavek_max_tiles")) enc->wavek_max_tiles = value < 0 ? 0 : (value > aae_host::kWaveKTileCap ? aae_host::kWaveKTileCap : value);
-    else if (!strcmp(name, "wavek_narrow_max_tiles")) enc->wavek_narrow_max_tiles = value < 0 ? 0 : value;
-    else if (!strcmp(name, "wavek_target_blocks")) enc->wavek_target_blocks = value < 0 ? 0 : (value > 2 * aae_host::kLayerTicketWords ? 2 * aae_host::kLayerTicketWords : value);
-    else if (!strcmp(name, "wavek_tiny_max_tiles")) enc->wavek_tiny_max_tiles = value < 0 ? 0 : value;
-    else if (!strcmp(name, "wavek_waves")) {
-        if (value != 4 && value != 8) return fail(AAE_ERR_INVALID, "wavek_waves %d: 4 or 8", value);
-        enc->wavek_waves = value;
-    } else if (!strcmp(name, "wavek_pingpong")) enc->wavek_pingpong = value ? 1 : 0;
-    else if (!strcmp(name, "wavek_spread")) enc->wavek_spread = value & 3;       // bit 0: 64 x 64 tiles, bit 1: 32 x 32 tiles (two accumulator chains)
-    else if (!strcmp(name, "wavek_tiny_waves")) {
-        if (value != 4 && value != 8) return fail(AAE_ERR_INVALID, "wavek_tiny_waves %d: 4 or 8", value);
-        enc->wavek_tiny_waves = value;
-    } else if (!strcmp(name, "wavek_depth")) {
-        if (value != 2 && value != 3) return fail(AAE_ERR_INVALID, "wavek_depth %d: 2 or 3", value);
-        enc->wavek_depth = value;
-    }
-    else if (!strcmp(name, "igemm_breg_wide")) enc->igemm_breg_wide = value ? 1 : 0;
-    else if (!strcmp(name, "igemm_breg_wide_min_blocks")) enc->igemm_breg_wide_min_blocks = value;
-    else if (!strcmp(name, "igemm_breg_min_blocks")) enc->igemm_breg_min_blocks = value;
-    else if (!strcmp(name, "first_vec4")) enc->first_vec4 = value ? 1 : 0;
-    else if (!strcmp(name, "first_group_split_max_tiles")) enc->first_group_split_max_tiles = value < 0 ? 0 : value;
-    else if (!strcmp(name, "first_target_blocks")) enc->first_target_blocks = value < 1 ? 1 : value;
-    else if (!strcmp(name, "first_max_tiles_per_block")) enc->first_max_tiles_per_block = value < 1 ? 1 : value;
-    else if (!strcmp(name, "x3h_act_shift")) {
-        if (value < -8 || value > 12) return fail(AAE_ERR_INVALID, "x3h_act_shift %d outside [-8, 12]", value);
-        enc->x3h_act_shift = value;
-    } else if (!strcmp(name, "winograd")) {
+#endif
+    if (!strcmp(name, "winograd")) {
         if (value != 0) {
             bool any = false;
             for (const Layer& L : enc->layers) any = any || L.wino_geom >= 0;
             if (!any) return fail(AAE_ERR_UNSUPPORTED, "winograd: no layer is eligible (5 x 5 stride-2 'SAME' layers behind the first one with 32 | Cin, 64 | Cout and 16 | Ho, Wo or an 8 x 8 output)");
         }
-        if (value < 0 || value > 2) return fail(AAE_ERR_INVALID, "winograd %d: 0 = direct kernels, 1 = one launch per layer, 2 = one launch per polyphase component", value);
 #ifndef AAE_EXPERIMENTS
         if (value == 2) return fail(AAE_ERR_UNSUPPORTED, "option 'winograd' = 2 (one launch per polyphase component: measured slower) is a kernel variant of the experiments build (-DAAE_EXPERIMENTS)");
 #endif
-        enc->winograd = value;
-    } else if (!strcmp(name, "winograd_wide")) {
-        enc->winograd_wide = value ? 1 : 0;
-    } else if (!strcmp(name, "winograd_stage32")) {
-        enc->winograd_stage32 = value ? 1 : 0;
-    } else if (!strcmp(name, "winograd_static_halo")) {
-        enc->winograd_static_halo = value ? 1 : 0;
-    } else if (!strcmp(name, "winograd_min_batch")) {
-        enc->winograd_min_batch = value < 1 ? 1 : value;
-    } else if (!strcmp(name, "winograd_min_fill_pct")) {
-        enc->winograd_min_fill_pct = value < 1 ? 1 : (value > 100 ? 100 : value);
-    } else if (!strcmp(name, "winograd_min_blocks")) {
-        enc->winograd_min_blocks = value < 0 ? 0 : value;
-    } else if (!strcmp(name, "multi_mid_group")) {
-        enc->multi_mid_group = value ? 1 : 0;
-    } else if (!strcmp(name, "multi_split_items")) {
-        enc->multi_split_items = value ? 1 : 0;
-    } else if (!strcmp(name, "multi_group_winograd")) {
-        enc->multi_group_winograd = value ? 1 : 0;
-    } else if (!strcmp(name, "multi_mid_scan")) {
-        enc->multi_mid_scan = value ? 1 : 0;
-    } else if (!strcmp(name, "multi_mid_ragged")) {
-        enc->multi_mid_ragged = value ? 1 : 0;
-    } else if (!strcmp(name, "winograd_xcd_cols")) {
-        if (value < -1 || value > 8) return fail(AAE_ERR_INVALID, "winograd_xcd_cols %d: -1 = per-layer default, 0 = plain block order, 1 ... 8 = column blocks of a region per XCD", value);
-        enc->winograd_xcd_cols = value;
-    } else if (!strcmp(name, "precision")) {
-        if (value < 0 || value > 2) return fail(AAE_ERR_INVALID, "precision %d: 0 = fp32, 1 = f32x3h, 2 = f32x3h where it is faster", value);
-        if (value != 0) {
-            bool ok = enc->layers[0].kind == KIND_FIRST_MFMA && enc->dense.kind == KIND_IGEMM;
-            for (size_t i = 1; i < enc->layers.size(); ++i) ok = ok && enc->layers[i].kind == KIND_IGEMM;
-            if (!ok) return fail(AAE_ERR_UNSUPPORTED, "f32x3h needs the matrix-core kernels on every layer (first layer 5x5 with C in {1,3}, later Cin %% 32 == 0)");
-        }
-        enc->precision = value;
     }
-    else return fail(AAE_ERR_INVALID, "unknown encoder option '%s'", name);
-    return AAE_OK;
+    if (!strcmp(name, "precision") && (value == 1 || value == 2)) {
+        bool ok = enc->layers[0].kind == KIND_FIRST_MFMA && enc->dense.kind == KIND_IGEMM;
+        for (size_t i = 1; i < enc->layers.size(); ++i) ok = ok && enc->layers[i].kind == KIND_IGEMM;
+        if (!ok) return fail(AAE_ERR_UNSUPPORTED, "f32x3h needs the matrix-core kernels on every layer (first layer 5x5 with C in {1,3}, later Cin %% 32 == 0)");
+    }
+    char err[256];
+    const int rc = apply_option(*enc, name, value, err, sizeof(err));
+    return rc == AAE_OK ? AAE_OK : fail(rc, "%s", err);
 }
 
 size_t aae_encoder_workspace_bytes(const aae_encoder* enc, int B) {
@@ -538,9 +421,8 @@ int aae_codebook_prepare_upright(aae_codebook* cb, int col_stride, void* stream_
             sub->E = static_cast<float*>(p);
             cb->upright_copies.push_back({col_stride, sub});
         }
-        sub->scan_mode = cb->scan_mode; sub->scan_ticket = cb->scan_ticket; sub->topk_prune = cb->topk_prune; sub->cu_count = cb->cu_count;
-        sub->scan_walk = cb->scan_walk; sub->scan_fused_norm = cb->scan_fused_norm; sub->scan_rh4 = cb->scan_rh4; sub->scan_resident_fin = cb->scan_resident_fin;
-        sub->scan_topk_stream = cb->scan_topk_stream;
+        static_cast<ScanSettings&>(*sub) = *cb;
+        sub->cu_count = cb->cu_count;
         cb->upright = sub; cb->upright_stride = col_stride;
     }
     if (int rc = gather_upright_rows(cb, cb->upright, cb->upright_stride, stream)) return rc;
@@ -570,27 +452,9 @@ void aae_codebook_destroy(aae_codebook* cb) {
 int aae_codebook_set_scan_mode(aae_codebook* cb, int mode) {
     using namespace aae_host;
     if (!cb) return fail(AAE_ERR_INVALID, "aae_codebook_set_scan_mode: null handle");
-    if (mode != AAE_SCAN_AUTO && mode != AAE_SCAN_GEMV && mode != AAE_SCAN_MFMA && mode != AAE_SCAN_STREAM && mode != AAE_SCAN_STREAM_2L &&
-        mode != AAE_SCAN_AUTO_NO_PRUNE && mode != AAE_SCAN_STREAM_WALK && mode != AAE_SCAN_AUTO_PACKED && mode != AAE_SCAN_AUTO_RH2 && mode != AAE_SCAN_AUTO_FIN && mode != AAE_SCAN_AUTO_TOPK_ROWS)
-        return fail(AAE_ERR_INVALID, "scan mode %d", mode);
-#ifndef AAE_EXPERIMENTS
-    if (mode == AAE_SCAN_GEMV || mode == AAE_SCAN_STREAM_WALK)
-        return fail(AAE_ERR_UNSUPPORTED, "scan mode %d (the round-1 shuffle-reduction scan / the walking stream scan: measured slower) exists in the experiments build only (-DAAE_EXPERIMENTS)", mode);
-#endif
-    cb->scan_ticket = mode == AAE_SCAN_STREAM_2L ? 0 : 1;
-    cb->topk_prune = mode == AAE_SCAN_AUTO_NO_PRUNE ? 0 : 1;
-    cb->scan_walk = mode == AAE_SCAN_STREAM_WALK ? 1 : 0;
-    cb->scan_fused_norm = mode == AAE_SCAN_AUTO_PACKED ? 0 : 1;
-    cb->scan_rh4 = mode == AAE_SCAN_AUTO_RH2 ? 0 : 1;
-    cb->scan_resident_fin = mode == AAE_SCAN_AUTO_FIN ? 1 : 0;
-    cb->scan_topk_stream = mode == AAE_SCAN_AUTO_TOPK_ROWS ? 0 : 1;
-    cb->scan_mode = (mode == AAE_SCAN_STREAM_2L || mode == AAE_SCAN_STREAM_WALK) ? AAE_SCAN_STREAM
-                    : ((mode == AAE_SCAN_AUTO_NO_PRUNE || mode == AAE_SCAN_AUTO_PACKED || mode == AAE_SCAN_AUTO_RH2 || mode == AAE_SCAN_AUTO_FIN || mode == AAE_SCAN_AUTO_TOPK_ROWS) ? AAE_SCAN_AUTO : mode);
-    for (auto& c : cb->upright_copies) {
-        c.second->scan_mode = cb->scan_mode; c.second->scan_ticket = cb->scan_ticket; c.second->topk_prune = cb->topk_prune; c.second->scan_walk = cb->scan_walk;
-        c.second->scan_fused_norm = cb->scan_fused_norm; c.second->scan_rh4 = cb->scan_rh4; c.second->scan_resident_fin = cb->scan_resident_fin;
-        c.second->scan_topk_stream = cb->scan_topk_stream;
-    }
+    char err[256];
+    if (const int rc = apply_scan_mode(*cb, mode, err, sizeof(err))) return fail(rc, "%s", err);     // (aae_options.h: kScanModeTable)
+    for (auto& c : cb->upright_copies) static_cast<ScanSettings&>(*c.second) = *cb;
     return AAE_OK;
 }
 

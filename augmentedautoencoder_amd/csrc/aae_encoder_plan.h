@@ -196,14 +196,10 @@ static unsigned next_nonce() {
 // Ticket words at the front of every encoder workspace: a range of single words per layer (conv layers 0..7, then
 // the dense layer) for the wave-split-K tiles, then one two-level slot per 128-column tile of the dense GEMV.  Every
 // ticketed launch has its own words, so the first kernel of a forward can prepare all of them (TicketPrep).
-constexpr int kChainMaxBlocks = 1024;       // upper bound of the persistent per-detection launch's grid (option detect_chain_blocks)
 constexpr int kGemvTicketSlots = 8;
-constexpr int kLayerTicketWords = 256;     // per layer: one word per output tile of a split layer (split => at most 128 tiles)
 constexpr size_t kConvTicketBytes = (size_t)(AAE_MAX_LAYERS + 1) * kLayerTicketWords * 8;
 constexpr size_t kGemvTicketBytes = (size_t)kGemvTicketSlots * aae::kTicketSlotWords * 8;
 constexpr size_t kTicketBytes = kConvTicketBytes + kGemvTicketBytes + (size_t)aae::kGridBarrierWords * 8;    // ... then the grid barrier of the persistent per-detection launch
-
-constexpr int kWaveKTileCap = 8192;        // 64 x 64 output tiles the wave-split-K kernel is ever asked to walk (option wavek_max_tiles is clamped to it)
 
 // Launch plan of the wave-split-K igemm (conv_wavek_f32.h) for a layer at M rows, or use == false.
 struct WaveKPlan {

@@ -79,6 +79,8 @@
  *   "ticket_prep" (1): conv1 installs the ticket nonces of the later launches of its call (0: every launch installs its own)
  *   "multi_force_shape" (0), "multi_force_g" (0): A/B of the grouped query's plan (tools/multi_plan_ab.py): wave tile (one nibble per conv
  *                        layer: 1 = 32 x 32, 2 = 64 x 32, 3 = 64 x 64) / K split (one byte per conv layer) forced
+ *   "multi_force_depth" (0): A/B -- slabs in flight of the group plan's 64 x 32 layers (one nibble per conv layer)
+ *   "multi_xcd_affine" (1): grouped query of 8 | 16 equal-sized objects -- all blocks of an object on one XCD (conv_wavek_f32.h, ConvWaveKMultiArgs)
  *   [experiments] "wavek_waves" (4 | 8), "wavek_tiny_waves" (4 | 8), "wavek_depth" (2 | 3), "wavek_pingpong" (0), "wavek_spread" (3):
  *                        eight waves per block, three slabs in flight, the barrier-paced schedule, the burst load schedules -- each
  *                        measured slower than the default beside it (CHANGELOG.md rounds 2-4)

@@ -3,3 +3,14 @@
 #include "hip_emu.h"
 
 #include "../../augmentedautoencoder_amd/csrc/aae_hip_impl.h"
+
+// (tests/test_options.py) the eight ScanSettings fields of a codebook handle (col_stride <= 1) or of its upright copy for col_stride
+extern "C" int aae_emu_codebook_scan_settings(const aae_codebook* cb, int col_stride, int* out8) {
+    const aae_host::ScanSettings* s = col_stride <= 1 ? cb : nullptr;
+    for (const auto& c : cb->upright_copies)
+        if (c.first == col_stride) s = c.second;
+    if (!s) return AAE_ERR_INVALID;
+    const int v[8] = {s->scan_mode, s->scan_ticket, s->topk_prune, s->scan_walk, s->scan_fused_norm, s->scan_rh4, s->scan_resident_fin, s->scan_topk_stream};
+    memcpy(out8, v, sizeof(v));
+    return AAE_OK;
+}
