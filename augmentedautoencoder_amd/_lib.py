@@ -19,6 +19,8 @@ AAE_SCAN_AUTO, AAE_SCAN_GEMV, AAE_SCAN_MFMA, AAE_SCAN_STREAM, AAE_SCAN_STREAM_2L
 AAE_SCAN_AUTO_PACKED, AAE_SCAN_AUTO_RH2, AAE_SCAN_AUTO_FIN, AAE_SCAN_AUTO_TOPK_ROWS = 7, 8, 9, 10
 AAE_ABI_VERSION = 3
 AAE_MODEL_RECONST, AAE_MODEL_CAD = 0, 1
+AAE_ICP_MAX_PROBLEMS, AAE_ICP_MAX_POINTS = 16, 4096
+AAE_ICP_DEPTH_ONLY, AAE_ICP_NO_DEPTH, AAE_ICP_NO_DEPTH_ZERO_T = 1, 2, 4
 
 LIB_NAME = 'libaae_hip.so'
 # the same sources with -DAAE_EXPERIMENTS: every kernel variant that measured slower than the defaults + the profiling / ablation
@@ -46,6 +48,7 @@ EXPORTED_SYMBOLS = (
     'aae_decoder_forward_timed', 'aae_decoder_kernel_label', 'aae_decoder_kernel_flops', 'aae_decoder_activation_info',
     'aae_mesh_create', 'aae_mesh_destroy', 'aae_render_workspace_bytes', 'aae_render_embedding_views', 'aae_render_embedding_views_timed',
     'aae_render_frames',
+    'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
 )
 
 
@@ -79,6 +82,11 @@ class RenderParams(Structure):
     """aae_render_params"""
     _fields_ = [('K', c_double * 9), ('t', c_double * 3), ('W', c_int32), ('H', c_int32), ('clip_near', c_double), ('clip_far', c_double),
                 ('pad_factor', c_double), ('light', c_float * 3), ('ambient', c_float), ('diffuse', c_float), ('specular', c_float)]
+
+
+class IcpShape(Structure):
+    """aae_icp_shape"""
+    _fields_ = [('n_problems', c_int32), ('max_points', c_int32), ('W', c_int32), ('H', c_int32), ('crop_w', c_int32), ('crop_h', c_int32)]
 
 
 class MultiItem(Structure):
@@ -219,6 +227,23 @@ def declare_render(lib):
     return lib
 
 
+def declare_icp(lib):
+    """The depth refinement's entry points (aae_icp.hip: like the rasteriser, part of the GPU library only)."""
+    lib.aae_icp_workspace_bytes.restype = c_size_t
+    lib.aae_icp_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
+    lib.aae_icp_workspace_info.restype = c_int
+    lib.aae_icp_workspace_info.argtypes = [POINTER(IcpShape), c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]
+    lib.aae_icp_prepare.restype = c_int
+    lib.aae_icp_prepare.argtypes = [POINTER(IcpShape), c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_size_t, c_void_p]
+    refine = [POINTER(IcpShape), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+              c_void_p, c_size_t, c_void_p]
+    lib.aae_icp_refine.restype = c_int
+    lib.aae_icp_refine.argtypes = refine
+    lib.aae_icp_refine_timed.restype = c_int
+    lib.aae_icp_refine_timed.argtypes = refine + [POINTER(c_float)]
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -239,7 +264,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare_render(declare(ctypes.CDLL(path)))
+    lib = declare_icp(declare_render(declare(ctypes.CDLL(path))))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -115,9 +115,13 @@ class _FrameStage(object):
 
 class AePoseEstimator(object):
 
-    def __init__(self, test_config_path=None, codebooks=None, train_args=None, upright=False, topk=1, camPose=False, share_workspaces=True):
+    def __init__(self, test_config_path=None, codebooks=None, train_args=None, upright=False, topk=1, camPose=False, share_workspaces=True,
+                 icp=False):
         """Either ``test_config_path`` (the m3 cfg with an [auto_pose] section, as in the
-        reference) or explicit ``codebooks`` / ``train_args`` dicts keyed by class name."""
+        reference) or explicit ``codebooks`` / ``train_args`` dicts keyed by class name.
+        ``icp``: False (also ``[auto_pose] icp`` absent or false), True (an ``icp.ICP`` over the classes' ``[Paths] model_path``
+        is built at first use) or an ``icp.ICP`` whose class order is that of the registered classes: process() then refines
+        every accepted detection with the depth image (``_refine_with_depth``)."""
         self._process_requirements = ['color_img', 'camK', 'bboxes']
         self.all_codebooks, self.all_train_args, self.pad_factors, self.patch_sizes = {}, {}, {}, {}
         self._image_format = {'color_format': 'bgr', 'color_data_type': np.uint8, 'depth_data_type': np.float32}
@@ -139,6 +143,7 @@ class AePoseEstimator(object):
             camPose = test_args.getboolean('auto_pose', 'camPose')
             upright = test_args.getboolean('auto_pose', 'upright')
             topk = test_args.getint('auto_pose', 'topk')
+            icp = icp or test_args.getboolean('auto_pose', 'icp', fallback=False)
             self.class_2_encoder = ast.literal_eval(test_args.get('auto_pose', 'class_2_encoder'))
             for clas_name, experiment in self.class_2_encoder.items():
                 full_name = experiment.split('/')
@@ -178,6 +183,52 @@ class AePoseEstimator(object):
         self.geometry_chunk = 16           # process(): classes with more than 2 x this many detections go to the GPU in chunks (_chunk_sizes), the last of this size
         if self._camPose:
             self._process_requirements.append('camPose')
+        self._icp = icp if icp else None               # None: process() never looks at depth_img
+        if self._icp is not None:
+            self._process_requirements.append('depth_img')
+
+    @property
+    def icp_handle(self):
+        """the ICP object of an estimator built with icp=True (ae_pose_estimator.py:188's icp_handle), created at first use"""
+        if self._icp is True:
+            from .icp import ICP
+            self._icp = ICP(None, [self.all_train_args[c] for c in self.all_train_args])
+        return self._icp
+
+    @staticmethod
+    def depth_crop(depth_img, box_xywh, pad_factor):
+        """The window of the depth image the refinement reads: the box's padded square clipped to the image, as
+        eval/eval_utils.py:104-117 slices it (Python 2: size / 2 floors, the float box halves do not)."""
+        H, W = depth_img.shape[:2]
+        x, y, w, h = box_xywh
+        size = int(np.maximum(h, w) * pad_factor)
+        left, right = int(np.max([x + w / 2. - size // 2, 0])), int(np.min([x + w / 2. + size // 2, W]))
+        top, bottom = int(np.max([y + h / 2. - size // 2, 0])), int(np.min([y + h / 2. + size // 2, H]))
+        return depth_img[top:bottom, left:right]
+
+    def _refine_with_depth(self, poses, idcs, accepted, classes, depth_img, camK, dims):
+        """eval/ae_eval.py:192-210 (the commented block of ae_pose_estimator.py:175-198) for every accepted detection, batched
+        per class: ICP along z -> the translation again with depth_pred = the refined t_z -> rotation ICP.  depth_img in
+        millimetres.  A detection whose depth window is empty keeps its RGB pose."""
+        handle = self.icp_handle
+        order = list(self.all_train_args)
+        for clas in classes:
+            members = [(j, bb) for j, c, bb in accepted if c == clas]
+            crops = [self.depth_crop(depth_img, bb, self.pad_factors[clas]) for _, bb in members]
+            keep = [k for k, c in enumerate(crops) if c.size > 0]
+            if not keep:
+                continue
+            members, crops = [members[k] for k in keep], [crops[k] for k in keep]
+            Rs, ts = [poses[j][1] for j, _ in members], [poses[j][2] for j, _ in members]
+            ci = order.index(clas)
+            first = handle.icp_refinement_batch(crops, Rs, ts, camK, dims, depth_only=True, clas_idx=ci)
+            codebook = self.all_codebooks[clas]
+            _, ts2 = codebook.poses_from_indices(np.array([idcs[j] for j, _ in members]), [bb for _, bb in members], camK, self.all_train_args[clas],
+                                                 depth_preds=[t[2] for _, t in first])
+            second = handle.icp_refinement_batch(crops, [R for R, _ in first], list(ts2), camK, dims, no_depth=True, clas_idx=ci)
+            for k, (j, _) in enumerate(members):
+                poses[j] = (clas, second[k][0], ts2[k])
+        return poses
 
     def _chunk_plan(self, counts):
         """How the detections of a frame go to the GPU: ``counts`` = detections per class in launch order -> chunk sizes per
@@ -309,7 +360,12 @@ class AePoseEstimator(object):
         classes = sorted(set(c for _, c, _ in accepted))
         first = self.all_codebooks[classes[0]]
         device = getattr(first._encoder.engine, 'device', None)
-        if isinstance(frame, np.ndarray) and device is not None and getattr(device, 'type', 'cpu') == 'cuda' and all(
+        if self._icp is not None and depth_img is not None:
+            # the refinement needs the matched rows again (the second translation) and dwarfs the RGB part: the plain path keeps them
+            idcs = {}
+            poses = self._process_plain(accepted, classes, frame, off_x, off_y, camK, idcs_out=idcs)
+            poses = self._refine_with_depth(poses, idcs, accepted, classes, np.asarray(depth_img), camK, (W, H))
+        elif isinstance(frame, np.ndarray) and device is not None and getattr(device, 'type', 'cpu') == 'cuda' and all(
                 getattr(self.all_codebooks[c]._encoder.engine, 'device', None) == device for c in classes):
             poses = self._process_staged(accepted, classes, frame, off_x, off_y, camK, device)
         else:
@@ -325,7 +381,7 @@ class AePoseEstimator(object):
             out.append(PoseEstimate(name=clas, trafo=H_est))
         return out
 
-    def _process_plain(self, accepted, classes, frame, off_x, off_y, camK):
+    def _process_plain(self, accepted, classes, frame, off_x, off_y, camK, idcs_out=None):
         """{detection index: (class, R [3,3], t [3])} through the public Codebook calls (any engine, e.g. the CPU doubles of the tests)"""
         image_dev = None
         poses = {}
@@ -345,6 +401,8 @@ class AePoseEstimator(object):
                 Rs, ts = [r.squeeze() for r, _ in per], [t.squeeze() for _, t in per]
             for k, (j, _) in enumerate(members):
                 poses[j] = (clas, Rs[k], ts[k])
+                if idcs_out is not None:
+                    idcs_out[j] = int(idcs[k])
         return poses
 
     @staticmethod

@@ -393,6 +393,62 @@ int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, 
                       void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* ---- Depth ICP refinement ---------------------------------------------------------------------------
+ * Replaces icp_refinement's point clouds, filter and ICP loop (auto_pose/eval/icp_utils.py:96-175,248-274 and the
+ * same code in auto_pose/icp/icp.py) for up to AAE_ICP_MAX_PROBLEMS detections per call, all in float64
+ * (csrc/kernels/icp_core.h states the arithmetic and the exactness rule).  The caller renders the synthetic depth
+ * (aae_render_frames), decides "too few points", draws the subsample and composes the pose: the random numbers and
+ * the 4x4 products stay on the host.  Nearest neighbours are exact; among equidistant targets the lowest index wins
+ * (the reference's KD-tree answers any of them).
+ * The workspace may hold anything on entry; no allocation and no synchronisation inside a call. */
+#define AAE_ICP_MAX_PROBLEMS 16
+#define AAE_ICP_MAX_POINTS 4096   /* subsampled points of one problem (the reference draws at most 3000)          */
+#define AAE_ICP_DEPTH_ONLY 1      /* best_fit_transform(depth_only=True): R = I, t = (0, 0, dz)                   */
+#define AAE_ICP_NO_DEPTH 2        /* no_depth=True, eval/icp_utils.py:60-61: t = (t_x, t_y, 0)                    */
+#define AAE_ICP_NO_DEPTH_ZERO_T 4 /* with AAE_ICP_NO_DEPTH, icp/icp.py:58-61: t = (0, 0, 0)                        */
+
+typedef struct aae_icp_shape {
+    int32_t n_problems;           /* 1 ... AAE_ICP_MAX_PROBLEMS                                                   */
+    int32_t max_points;           /* 3 ... AAE_ICP_MAX_POINTS: the largest subsample of a problem                 */
+    int32_t W, H;                 /* the synthetic depth frames                                                   */
+    int32_t crop_w, crop_h;       /* the largest depth crop (a crop of h x w needs h * w <= crop_w * crop_h)      */
+} aae_icp_shape;
+
+size_t aae_icp_workspace_bytes(int n_problems, int max_points, int W, int H, int crop_w, int crop_h);
+
+/* Steps 1-3.  syn_depth device float32 [P,H,W] (rendered at R_est, t = (0, 0, t_z)); crop_depth device float32
+ * [P, crop_w * crop_h], crop p dense (crop_dims[2p] rows x crop_dims[2p+1] columns, host int32) at the front of its
+ * slot; K host float64 [9] (K_test); max_mean_dist_factor 2.0 or 4.0.  Per problem the workspace then holds the
+ * synthetic points (depth != 0, row-major order, misc.py:65-70), their centroid and largest distance, and the real
+ * points of the crop (principal point (rows / 2, columns / 2) floored, as the reference sets it) nearer to the
+ * centroid than factor * that distance, in order.  counts_out: host int32 [P,2] (synthetic, real), written by a copy
+ * queued on `stream` (pinned memory keeps it asynchronous): valid once the stream has reached it. */
+int aae_icp_prepare(const aae_icp_shape* shape, const float* syn_depth, const float* crop_depth, const int32_t* crop_dims,
+                    const double* K, double max_mean_dist_factor, int32_t* counts_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* where a prepared workspace keeps problem `problem`'s data (for the tests and for callers that want the clouds):
+ * what = 0 synthetic points (float64 [count,3]), 1 real points, 2 (centroid[3], largest distance, threshold) float64 [5] */
+int aae_icp_workspace_info(const aae_icp_shape* shape, int problem, int what, size_t* offset_bytes, size_t* capacity);
+
+/* Steps 5-6 on a prepared workspace: icp(A = syn[sub_syn], B = real[sub_real], tolerance) per problem.  n_points host
+ * int32 [P] (3 ... max_points, or 0 for a problem to leave out: T = identity, i = -1; else AAE_ERR_INVALID); sub_syn / sub_real device int32 [P, max_points] (an index outside
+ * [0, count) is clamped and sets bit 0 of error_out[p]); modes host int32 [P] (AAE_ICP_* flags).  Queues one gather,
+ * max_iterations icp_step launches (a converged problem's blocks return at once) and one finish, with no host round trip:
+ * intended to be capturable, not yet exercised under capture.
+ * Outputs, device: T_out float64 [P,16] (row-major 4x4), iterations_out int32 [P] (the reference's i), mean_error_out
+ * float64 [P], error_out int32 [P], and optionally (or NULL) the last iteration's distances float64 [P, max_points]
+ * and matched target indices int32 [P, max_points]. */
+int aae_icp_refine(const aae_icp_shape* shape, const int32_t* n_points, const int32_t* sub_syn, const int32_t* sub_real,
+                   const int32_t* modes, int max_iterations, double tolerance, double* T_out, int32_t* iterations_out,
+                   double* mean_error_out, int32_t* error_out, double* d2_out, int32_t* idx_out, void* workspace,
+                   size_t ws_bytes, void* stream);
+/* the same call with the time of each launch (gather, max_iterations steps, finish: max_iterations + 2 floats) from
+ * events on `stream`; synchronises, so not for capture */
+int aae_icp_refine_timed(const aae_icp_shape* shape, const int32_t* n_points, const int32_t* sub_syn, const int32_t* sub_real,
+                         const int32_t* modes, int max_iterations, double tolerance, double* T_out, int32_t* iterations_out,
+                         double* mean_error_out, int32_t* error_out, double* d2_out, int32_t* idx_out, void* workspace,
+                         size_t ws_bytes, void* stream, float* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
