@@ -599,6 +599,15 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
     return tm.mark();
 }
 
+// The round-fill rule on a block count: do `blocks` Winograd blocks fill winograd_min_fill_pct per cent of the rounds they occupy (winograd_rule has the
+// measurements; winograd_min_blocks > 0 -- tests, A/B -- asks for a plain count instead)?  Each caller counts its OWN way, and the three counts stay different:
+// winograd_rule and mid_group_layers (aae_multi_impl.h) count regions x Cout / 64 -- the latter only the complete regions where the ragged blocks leave the
+// launch --, plan_multi's per-detection group pass counts the XCD-padded grid (wino_grid_blocks).
+static bool wino_fills(const aae_encoder* enc, long long blocks) {
+    if (enc->winograd_min_blocks > 0) return blocks >= enc->winograd_min_blocks;
+    const long long cus = wavek_round_blocks(enc), rounds = (blocks + cus - 1) / cus;
+    return 100 * blocks >= (long long)enc->winograd_min_fill_pct * rounds * cus;
+}
 static bool winograd_rule(const aae_encoder* enc, const Layer& L, int B);
 static bool runs_winograd(const aae_encoder* enc, const Layer& L, int B) { return L.wino[0] && winograd_rule(enc, L, B); }
 // would any conv layer of a batch of B take the Winograd form, were its weights there?
@@ -635,10 +644,7 @@ static bool winograd_rule(const aae_encoder* enc, const Layer& L, int B) {
     // direct / Winograd = 1.65-1.85 at full rounds, 1.0 where the blocks fill half of the rounds they occupy): a layer gains when its blocks
     // fill at least winograd_min_fill_pct (56) per cent of their rounds -- default net: conv2 from B = 9, conv3 from 18, conv4 (four images
     // per block) from 69, and e.g. not conv3 at B = 33 ... 35 or conv4 at B = 129 ... 140 (a new round for a few blocks)
-    const long long blocks = (long long)(L.Cout / 64) * (L.wino_geom == 0 ? (long long)(L.Ho / 16) * (L.Wo / 16) * B : (long long)ceil_div(B, 4));
-    if (enc->winograd_min_blocks > 0) return blocks >= enc->winograd_min_blocks;
-    const long long cus = wavek_round_blocks(enc), rounds = (blocks + cus - 1) / cus;
-    return 100 * blocks >= (long long)enc->winograd_min_fill_pct * rounds * cus;
+    return wino_fills(enc, (long long)(L.Cout / 64) * (L.wino_geom == 0 ? (long long)(L.Ho / 16) * (L.Wo / 16) * B : (long long)ceil_div(B, 4)));
 }
 
 // layer_begin / layer_end: run only the layers [layer_begin, layer_end) of the chain -- conv layers 0 ... nl - 1, the dense layer = nl; x is

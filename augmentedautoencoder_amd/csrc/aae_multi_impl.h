@@ -53,6 +53,11 @@ struct MultiPlan {
 static thread_local int t_multi_launches = 0;      // kernel launches queued by the calling thread's last multi call (its grouped part)
 
 static int wavek_shape_key(const WaveKPlan& w) { return (w.MT == 1 ? 1000 : 0) + w.NT * 100 + w.waves * 10 + w.depth; }
+// Is the plan's wave tile one of the instantiated grouped forms (launch_wavek_multi: the defaults -- 4 waves, 2 slabs in flight, the spread schedules)?
+static bool wavek_multi_instantiated(const aae_encoder* enc, const WaveKPlan& w) {
+    const int key = wavek_shape_key(w);
+    return w.use && w.waves == 4 && w.depth == 2 && ((key == 1142 && (enc->wavek_spread & 2)) || key == 142 || (key == 242 && (enc->wavek_spread & 1)));
+}
 
 // Can the scan of (cb, n detections, col_stride) run as one object's share of scan_stream_multi_kernel?
 static bool multi_scan_groupable(const aae_codebook* cb, int n, int col_stride, const aae_codebook** eff_out, int* idx_scale) {
@@ -89,12 +94,9 @@ static bool multi_encoder_groupable(const aae_encoder* enc, int n, std::vector<W
         const Layer& L = enc->layers[li];
         if (L.kind != KIND_IGEMM) return false;
         const WaveKPlan w = plan_wavek(enc, L, (long long)n * L.Ho * L.Wo, false);
-        if (!w.use || w.waves != 4 || w.depth != 2) return false;
-        const int key = wavek_shape_key(w);
-        const bool spread = key == 1142 ? (enc->wavek_spread & 2) != 0 : (key == 242 ? (enc->wavek_spread & 1) != 0 : false);
-        if (!((key == 1142 && spread) || key == 142 || (key == 242 && spread))) return false;         // (the instantiated grouped forms = the defaults)
+        if (!wavek_multi_instantiated(enc, w)) return false;
         plans[li] = w;
-        sig.push_back(enc->multi_group_plan ? 0 : key);
+        sig.push_back(enc->multi_group_plan ? 0 : wavek_shape_key(w));
     }
     return true;
 }
@@ -182,13 +184,13 @@ static Workspace plan_workspace_grouped(const aae_encoder* enc, int n, const std
 }
 
 // Can (enc, n detections) join a mid-batch group?  Default options in exact fp32, every conv layer behind the first one prepared for Winograd.
-// (weights_pending: asked before the Winograd-domain weights exist -- aae_multi_workspace_bytes builds them only for objects whose group would form)
-static bool multi_encoder_mid_groupable(const aae_encoder* enc, int n, std::vector<int>& sig, bool weights_pending = false) {
+// (weights_pending: asked before the Winograd-domain weights exist -- prepare_winograd_for_frame builds them only for objects whose group would form)
+static bool multi_encoder_mid_groupable(const aae_encoder* enc, int n, std::vector<int>& sig, bool weights_pending) {
     const size_t nl = enc->layers.size();
     if (n < 5 || nl < 2 || enc->winograd != 1 || enc->winograd_wide || !enc->multi_mid_group || runs_split(enc, n)) return false;
     for (size_t li = 1; li < nl; ++li) {
         const Layer& L = enc->layers[li];
-        if (L.kind != KIND_IGEMM || L.wino_geom < 0 || (!L.wino[0] && !weights_pending)) return false;      // (the weights: prepared by aae_multi_workspace_bytes)
+        if (L.kind != KIND_IGEMM || L.wino_geom < 0 || (!L.wino[0] && !weights_pending)) return false;
         if ((unsigned long long)n * L.H * L.W * L.Cin * sizeof(float) >= 0x7FFFFF00ull) return false;
     }
     sig.clear();
@@ -215,7 +217,6 @@ static bool mid_ragged_opens_a_round(const aae_encoder* enc0, const Layer& L, co
 // ... and which conv layers does the GROUP fill the chip on (the round-fill rule of runs_winograd, on the group's blocks)?  Those run as one Winograd launch across the objects;
 // the others (4 classes x 6 boxes: conv4's 64 blocks) run per object on whatever kernel the object's own forward takes.  A group forms when at least one layer passes.
 static std::vector<char> mid_group_layers(const aae_encoder* enc0, const std::vector<int>& counts) {
-    const long long cus = wavek_round_blocks(enc0);
     std::vector<char> pass(enc0->layers.size(), 0);
     for (size_t li = 1; li < enc0->layers.size(); ++li) {
         const Layer& L = enc0->layers[li];
@@ -223,9 +224,7 @@ static std::vector<char> mid_group_layers(const aae_encoder* enc0, const std::ve
         for (int n : counts) regions += wino_regions(L, n);
         long long complete = 0;
         if (mid_ragged_opens_a_round(enc0, L, counts, &complete)) regions = complete;      // (then the rule looks at the complete blocks: the others leave the launch)
-        const long long blocks = regions * (L.Cout / 64), rounds = (blocks + cus - 1) / cus;
-        if (enc0->winograd_min_blocks > 0) pass[li] = blocks >= enc0->winograd_min_blocks;   // (tests, A/B: a plain block count instead of the fill rule, as in runs_winograd)
-        else pass[li] = 100 * blocks >= (long long)enc0->winograd_min_fill_pct * rounds * cus;
+        pass[li] = wino_fills(enc0, regions * (L.Cout / 64));
     }
     return pass;
 }
@@ -239,10 +238,6 @@ static bool mid_group_fills(const aae_encoder* enc0, const std::vector<int>& cou
 // open one more ROUND of blocks than the complete ones need (config 4: {34, 26, 27, 32, 31, 32, 33, 41} -> 67 groups x 8 column blocks = 536 = three rounds for 24
 // blocks; the 61 complete groups = 488 fit two), the last n mod 4 images of every object go to ONE grouped wave-split-K launch (the per-detection chain's kernel,
 // a plan for the group: plan_wavek_group) behind the Winograd launch: 1.28 -> ~0.95 ms for conv4 of that frame.
-static bool wavek_multi_instantiated(const aae_encoder* enc, const WaveKPlan& w) {
-    const int key = wavek_shape_key(w);
-    return w.use && w.waves == 4 && w.depth == 2 && ((key == 1142 && (enc->wavek_spread & 2)) || key == 142 || (key == 242 && (enc->wavek_spread & 1)));
-}
 static void plan_mid_ragged(const aae_multi_item* items, MultiPlan& mp) {
     mp.mid_rem.assign(mp.mid_groups.size(), std::vector<char>());
     mp.mid_wino.assign(mp.mid_groups.size(), std::vector<char>());
@@ -309,7 +304,7 @@ static int plan_multi(const aae_multi_item* items, int n_items, bool scan_only, 
         if (p.grouped) {
             p.sp = plan_scan(p.eff, it.n, 1);
             p.cb_bytes = align_up(p.sp.total, 256);
-        } else if (!scan_only && multi_encoder_mid_groupable(it.enc, it.n, p.sig)) {
+        } else if (!scan_only && multi_encoder_mid_groupable(it.enc, it.n, p.sig, weights_pending)) {
             p.mid = true;                           // (a candidate: confirmed below once its group is known)
         }
     }
@@ -383,7 +378,6 @@ static int plan_multi(const aae_multi_item* items, int n_items, bool scan_only, 
             const size_t nl = enc0->layers.size();
             mp.group_wino[gi].assign(nl, 0);
             if (g.size() < 2 || !enc0->multi_group_plan || !enc0->multi_group_winograd || enc0->winograd != 1 || enc0->winograd_wide) continue;
-            const long long cus = wavek_round_blocks(enc0);
             for (size_t li = 1; li < nl; ++li) {
                 const Layer& L0 = enc0->layers[li];
                 if (L0.kind != KIND_IGEMM || L0.wino_geom < 0) continue;
@@ -399,9 +393,7 @@ static int plan_multi(const aae_multi_item* items, int n_items, bool scan_only, 
                 // (four-image blocks: an object with one box fills a quarter of its block -- the block count says nothing about the work then; with at most 16 objects
                 //  per group such a layer never reaches the rule today, the guard keeps it that way)
                 if (L0.wino_geom == 1 && enc0->winograd_min_blocks == 0 && 4 * images < 3 * 4 * regions) continue;
-                const long long blocks = aae::wino_grid_blocks((int)regions, L0.Cout / 64, wino_xcd_cols(enc0, L0)), rounds = (blocks + cus - 1) / cus;
-                const bool fills = enc0->winograd_min_blocks > 0 ? blocks >= enc0->winograd_min_blocks : 100 * blocks >= (long long)enc0->winograd_min_fill_pct * rounds * cus;
-                if (fills) mp.group_wino[gi][li] = 1;
+                mp.group_wino[gi][li] = wino_fills(enc0, aae::wino_grid_blocks((int)regions, L0.Cout / 64, wino_xcd_cols(enc0, L0)));
             }
         }
     mp.rows = row;
@@ -570,6 +562,67 @@ static int launch_scan_multi(const MultiPlan& mp, const std::vector<int>& member
     return AAE_OK;
 }
 
+// The wave-split-K problem table (per-detection conv layers, the handed-over images and the dense layer of a mid-batch group): one more object behind the `at` blocks so far
+static void wavek_multi_append(aae::ConvWaveKMultiArgs& m, int& at, const aae::ConvWaveKArgs& a, const WaveKPlan& w) {
+    const int k = m.range.n++;
+    m.item[k] = a;
+    m.item[k].timeline = nullptr;
+    m.nblk[k] = w.blocks();
+    m.range.first[k] = at;
+    at += (w.blocks() + 7) / 8 * 8;              // (every object's first block on XCD 0: xcd_remap counts from it)
+    m.range.first[k + 1] = at;
+}
+// ... and its launch: false where no grouped instantiation exists for the shape key (wavek_multi_instantiated).  `variants`: the encoder whose A/B options
+// reach the experiments build's extra forms (the per-detection conv layers; nullptr elsewhere)
+static bool launch_wavek_multi(int key, const aae::ConvWaveKMultiArgs& m, int tag, int nblk, hipStream_t stream, const aae_encoder* variants) {
+#ifdef AAE_EXPERIMENTS
+    // (A/B: the spread load schedule for 64 x 32 tiles -- loads between the MFMAs of its two accumulators: 8 x 1 434 against 400 us,
+    //  16 x 1 807 against 743: slower, as on single objects in round 4; profiles/r13_multi/depth_and_schedule_ab.jsonl)
+    if (variants && key == 142 && (variants->multi_force_depth & 0x10000)) { launch_wavek_multi_t<2, 1, true>(m, tag, nblk, stream); return true; }
+    // three slabs in flight for the 64 x 32 layers (option multi_force_depth): conv4 of a few-detection frame streams 26 MB of cold weights
+    // per object against 5 us of MFMA work -- more bytes in flight changed NOTHING (8 x 1: 397 vs 397 us, profiles/r13_multi/depth_ab.jsonl)
+    if (variants && key == 143) { launch_wavek_multi_t<2, 1, false, 3>(m, tag, nblk, stream); return true; }
+#endif
+    (void)variants;
+    switch (key) {
+        case 1142: launch_wavek_multi_t<1, 1, true>(m, tag, nblk, stream); return true;
+        case 142: launch_wavek_multi_t<2, 1, false>(m, tag, nblk, stream); return true;
+        case 242: launch_wavek_multi_t<2, 2, true>(m, tag, nblk, stream); return true;
+    }
+    return false;
+}
+
+// The Winograd problem table of conv layer li across `members` (a per-detection group or a mid-batch group): geometry, per-object pointers, the prefix sum over the
+// objects' regions; returns the grid.  complete_blocks_only: the objects' last n mod 4 images leave the launch (plan_mid_ragged)
+static int wino_multi_args(const aae_multi_item* items, const MultiPlan& mp, const std::vector<int>& members, size_t li, unsigned char* base, bool complete_blocks_only,
+                           aae::ConvWinoMultiArgs& m) {
+    const aae_encoder* enc0 = items[members[0]].enc;
+    const Layer& L0 = enc0->layers[li];
+    memset(&m, 0, sizeof(m));
+    aae::ConvWinoArgs& c = m.c;
+    c.H = L0.H; c.W = L0.W; c.Cin = L0.Cin; c.Cout = L0.Cout; c.Ho = L0.Ho; c.Wo = L0.Wo; c.relu = L0.relu;
+    c.blocks_x = L0.wino_geom == 0 ? L0.Wo / 16 : 1;
+    c.blocks_y = L0.wino_geom == 0 ? L0.Ho / 16 : 1;
+    int at = 0;
+    m.range.n = (int)members.size();
+    for (size_t k = 0; k < members.size(); ++k) {
+        const MultiItemPlan& p = mp.items[(size_t)members[k]];
+        const Layer& L = items[members[k]].enc->layers[li];
+        aae::ConvWinoObject& ob = m.obj[k];
+        ob.x = reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[li - 1]);
+        ob.out = reinterpret_cast<float*>(base + p.enc_off + p.ws.act_off[li]);
+        for (int q = 0; q < 4; ++q) ob.U4[q] = L.wino[q];
+        ob.bias = L.bias; ob.bn_scale = L.bn_scale; ob.bn_shift = L.bn_shift;
+        ob.B = complete_blocks_only ? p.n / 4 * 4 : p.n;
+        m.range.first[k] = at;
+        at += wino_regions(L, ob.B);
+    }
+    m.range.first[members.size()] = at;
+    c.regions = at;
+    c.xcd_cols = wino_xcd_cols(enc0, L0);
+    return aae::wino_grid_blocks(at, L0.Cout / 64, c.xcd_cols);
+}
+
 // conv1 ... dense of up to kMultiMax grouped items (equal signatures): one launch per layer
 static int launch_encoder_multi(const aae_multi_item* items, const MultiPlan& mp, const std::vector<int>& members, const std::vector<char>& wino_layers, const void* x, int x_dtype,
                                 float* z_out, unsigned char* base, unsigned nonce, hipStream_t stream) {
@@ -624,80 +677,36 @@ static int launch_encoder_multi(const aae_multi_item* items, const MultiPlan& mp
     // ---- conv2 ...: the wave-split-K kernel, every object with its own plan -- or, where the group's blocks fill the chip, the Winograd layer kernel across the objects
     for (size_t li = 1; li < nl; ++li) {
         if (li < wino_layers.size() && wino_layers[li]) {
-            const Layer& L0 = enc0->layers[li];
             aae::ConvWinoMultiArgs wm;
-            memset(&wm, 0, sizeof(wm));
-            aae::ConvWinoArgs& c = wm.c;
-            c.H = L0.H; c.W = L0.W; c.Cin = L0.Cin; c.Cout = L0.Cout; c.Ho = L0.Ho; c.Wo = L0.Wo; c.relu = L0.relu;
-            c.blocks_x = L0.wino_geom == 0 ? L0.Wo / 16 : 1;
-            c.blocks_y = L0.wino_geom == 0 ? L0.Ho / 16 : 1;
-            int wat = 0;
-            wm.range.n = (int)members.size();
-            for (size_t k = 0; k < members.size(); ++k) {
-                const MultiItemPlan& p = mp.items[(size_t)members[k]];
-                const Layer& L = items[members[k]].enc->layers[li];
-                aae::ConvWinoObject& ob = wm.obj[k];
-                ob.x = reinterpret_cast<const float*>(enc_base(k) + p.ws.act_off[li - 1]);
-                ob.out = reinterpret_cast<float*>(enc_base(k) + p.ws.act_off[li]);
-                for (int q = 0; q < 4; ++q) ob.U4[q] = L.wino[q];
-                ob.bias = L.bias; ob.bn_scale = L.bn_scale; ob.bn_shift = L.bn_shift; ob.B = p.n;
-                wm.range.first[k] = wat;
-                wat += wino_regions(L, p.n);
-            }
-            wm.range.first[members.size()] = wat;
-            c.regions = wat;
-            c.xcd_cols = wino_xcd_cols(enc0, L0);
-            wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(wat, L0.Cout / 64, c.xcd_cols), stream, wm, enc0->winograd_static_halo);
+            const int grid = wino_multi_args(items, mp, members, li, base, false, wm);
+            wino_layer_multi_launch(enc0->layers[li].wino_geom, enc0->winograd_stage32, grid, stream, wm, enc0->winograd_static_halo);
             AAE_HIP_TRY(hipGetLastError());
             ++t_multi_launches;
             continue;
         }
         aae::ConvWaveKMultiArgs m;
         memset(&m, 0, sizeof(m));
-        m.range.n = (int)members.size();
+        const int key0 = wavek_shape_key(mp.items[(size_t)members[0]].plans[li]);
         int at = 0;
         for (size_t k = 0; k < members.size(); ++k) {
             const aae_multi_item& it = items[members[k]];
             const MultiItemPlan& p = mp.items[(size_t)members[k]];
             const Layer& L = it.enc->layers[li];
             const WaveKPlan& w = p.plans[li];
-            m.item[k] = wavek_args(it.enc, L, w, reinterpret_cast<const float*>(enc_base(k) + p.ws.act_off[li - 1]), p.n * L.Ho * L.Wo,
-                                   reinterpret_cast<float*>(enc_base(k) + p.ws.act_off[li]), reinterpret_cast<float*>(enc_base(k) + p.ws.partial_off),
-                                   tickets_of(k) + li * kLayerTicketWords, nonce, (int)li);
-            m.item[k].timeline = nullptr;
-            if (wavek_shape_key(w) != wavek_shape_key(mp.items[(size_t)members[0]].plans[li]))       // (one kernel instantiation serves the launch)
+            if (wavek_shape_key(w) != key0)              // (one kernel instantiation serves the launch)
                 return fail(AAE_ERR_RUNTIME, "multi-object query: the members of a group disagree on the wave tile of conv%zu", li + 1);
-            m.nblk[k] = w.blocks();
-            m.range.first[k] = at;
-            at += (w.blocks() + 7) / 8 * 8;              // (every object's first block on XCD 0: xcd_remap counts from it)
+            wavek_multi_append(m, at, wavek_args(it.enc, L, w, reinterpret_cast<const float*>(enc_base(k) + p.ws.act_off[li - 1]), p.n * L.Ho * L.Wo,
+                                                 reinterpret_cast<float*>(enc_base(k) + p.ws.act_off[li]), reinterpret_cast<float*>(enc_base(k) + p.ws.partial_off),
+                                                 tickets_of(k) + li * kLayerTicketWords, nonce, (int)li), w);
         }
-        m.range.first[members.size()] = at;
-        m.xcd_affine = 0;
         if (enc0->multi_xcd_affine && members.size() % 8 == 0) {          // equal-sized objects, a multiple of 8 of them: one XCD per object
             const int nb = m.range.first[1] - m.range.first[0];
             bool equal = true;
             for (size_t k = 0; k < members.size(); ++k) equal = equal && m.range.first[k + 1] - m.range.first[k] == nb;
             if (equal) m.xcd_affine = nb;
         }
-        const WaveKPlan& w0 = mp.items[(size_t)members[0]].plans[li];
-        const int tag = li <= 3 ? (int)li : 0;
-        switch (wavek_shape_key(w0)) {
-            case 1142: launch_wavek_multi_t<1, 1, true>(m, tag, at, stream); break;
-            case 142:
-#ifdef AAE_EXPERIMENTS
-                // (A/B: the spread load schedule for 64 x 32 tiles -- loads between the MFMAs of its two accumulators: 8 x 1 434 against 400 us,
-                //  16 x 1 807 against 743: slower, as on single objects in round 4; profiles/r13_multi/depth_and_schedule_ab.jsonl)
-                if (enc0->multi_force_depth & 0x10000) { launch_wavek_multi_t<2, 1, true>(m, tag, at, stream); break; }
-#endif
-                launch_wavek_multi_t<2, 1, false>(m, tag, at, stream); break;
-#ifdef AAE_EXPERIMENTS
-            // three slabs in flight for the 64 x 32 layers (option multi_force_depth): conv4 of a few-detection frame streams 26 MB of cold weights
-            // per object against 5 us of MFMA work -- more bytes in flight changed NOTHING (8 x 1: 397 vs 397 us, profiles/r13_multi/depth_ab.jsonl)
-            case 143: launch_wavek_multi_t<2, 1, false, 3>(m, tag, at, stream); break;
-#endif
-            case 242: launch_wavek_multi_t<2, 2, true>(m, tag, at, stream); break;
-            default: return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped wave-split-K instantiation for shape key %d", wavek_shape_key(w0));
-        }
+        if (!launch_wavek_multi(key0, m, li <= 3 ? (int)li : 0, at, stream, enc0))
+            return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped wave-split-K instantiation for shape key %d", key0);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
     }
@@ -791,31 +800,10 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
             }
             continue;
         }
-        aae::ConvWinoMultiArgs m;
-        memset(&m, 0, sizeof(m));
-        aae::ConvWinoArgs& c = m.c;
-        c.H = L0.H; c.W = L0.W; c.Cin = L0.Cin; c.Cout = L0.Cout; c.Ho = L0.Ho; c.Wo = L0.Wo; c.relu = L0.relu;
-        c.blocks_x = L0.wino_geom == 0 ? L0.Wo / 16 : 1;
-        c.blocks_y = L0.wino_geom == 0 ? L0.Ho / 16 : 1;
-        int at = 0;
-        m.range.n = (int)members.size();
         const bool split = li < rem_layers.size() && rem_layers[li];
-        for (size_t k = 0; k < members.size(); ++k) {
-            const MultiItemPlan& p = mp.items[(size_t)members[k]];
-            const Layer& L = items[members[k]].enc->layers[li];
-            aae::ConvWinoObject& ob = m.obj[k];
-            ob.x = reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[li - 1]);
-            ob.out = reinterpret_cast<float*>(base + p.enc_off + p.ws.act_off[li]);
-            for (int q = 0; q < 4; ++q) ob.U4[q] = L.wino[q];
-            ob.bias = L.bias; ob.bn_scale = L.bn_scale; ob.bn_shift = L.bn_shift;
-            ob.B = split ? p.n / 4 * 4 : p.n;                                  // (split: the complete four-image blocks only)
-            m.range.first[k] = at;
-            at += wino_regions(L, ob.B);
-        }
-        m.range.first[members.size()] = at;
-        c.regions = at;
-        c.xcd_cols = wino_xcd_cols(enc0, L0);
-        wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, aae::wino_grid_blocks(at, L0.Cout / 64, c.xcd_cols), stream, m, enc0->winograd_static_halo);
+        aae::ConvWinoMultiArgs m;
+        const int grid = wino_multi_args(items, mp, members, li, base, split, m);
+        wino_layer_multi_launch(L0.wino_geom, enc0->winograd_stage32, grid, stream, m, enc0->winograd_static_halo);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
         if (split) {
@@ -823,8 +811,7 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
             aae::ConvWaveKMultiArgs r;
             memset(&r, 0, sizeof(r));
             const unsigned nonce = next_nonce();
-            int rat = 0, nk = 0;
-            const WaveKPlan* w0 = nullptr;
+            int rat = 0, key0 = 0;
             for (size_t k = 0; k < members.size(); ++k) {
                 const aae_multi_item& it = items[members[k]];
                 const MultiItemPlan& p = mp.items[(size_t)members[k]];
@@ -832,27 +819,14 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
                 const WaveKPlan& w = p.rem_plans[li];
                 const int full = p.n / 4 * 4, rem = p.n - full;
                 if (!rem || !w.use) continue;
-                if (!w0) w0 = &w;
+                if (!key0) key0 = wavek_shape_key(w);
                 unsigned long long* tickets = reinterpret_cast<unsigned long long*>(base + p.enc_off + p.ws.ticket_off) + li * kLayerTicketWords;
-                r.item[nk] = wavek_args(it.enc, L, w, reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[li - 1]) + (size_t)full * L.H * L.W * L.Cin, rem * L.Ho * L.Wo,
-                                        reinterpret_cast<float*>(base + p.enc_off + p.ws.act_off[li]) + (size_t)full * L.Ho * L.Wo * L.Cout,
-                                        reinterpret_cast<float*>(base + p.enc_off + p.rem_partial_off), tickets, nonce, (int)li);
-                r.item[nk].timeline = nullptr;
-                r.nblk[nk] = w.blocks();
-                r.range.first[nk] = rat;
-                rat += (w.blocks() + 7) / 8 * 8;
-                ++nk;
+                wavek_multi_append(r, rat, wavek_args(it.enc, L, w, reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[li - 1]) + (size_t)full * L.H * L.W * L.Cin,
+                                                      rem * L.Ho * L.Wo, reinterpret_cast<float*>(base + p.enc_off + p.ws.act_off[li]) + (size_t)full * L.Ho * L.Wo * L.Cout,
+                                                      reinterpret_cast<float*>(base + p.enc_off + p.rem_partial_off), tickets, nonce, (int)li), w);
             }
-            r.range.n = nk;
-            r.range.first[nk] = rat;
-            r.xcd_affine = 0;
-            const int tag = li <= 3 ? (int)li : 0;
-            switch (w0 ? wavek_shape_key(*w0) : 0) {
-                case 1142: launch_wavek_multi_t<1, 1, true>(r, tag, rat, stream); break;
-                case 142: launch_wavek_multi_t<2, 1, false>(r, tag, rat, stream); break;
-                case 242: launch_wavek_multi_t<2, 2, true>(r, tag, rat, stream); break;
-                default: return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped wave-split-K instantiation for the incomplete blocks of conv%zu", li + 1);
-            }
+            if (!launch_wavek_multi(key0, r, li <= 3 ? (int)li : 0, rat, stream, nullptr))
+                return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped wave-split-K instantiation for the incomplete blocks of conv%zu", li + 1);
             AAE_HIP_TRY(hipGetLastError());
             ++t_multi_launches;
         }
@@ -863,7 +837,6 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
     {
         aae::ConvWaveKMultiArgs m;
         memset(&m, 0, sizeof(m));
-        m.range.n = (int)members.size();
         const unsigned nonce = next_nonce();
         int at = 0, key0 = -1;
         for (size_t k = 0; k < members.size() && dense_grouped; ++k) {
@@ -873,32 +846,17 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
             const bool gemv = D.kind == KIND_IGEMM && p.n <= gemv_max_batch(it.enc) && it.enc->dense_gemv && D.K() % aae::kGemvChunk == 0;
             if (D.kind != KIND_IGEMM || gemv || !it.enc->wavek_dense) { dense_grouped = false; break; }
             const WaveKPlan w = plan_wavek(it.enc, D, p.n, false);
-            const int key = wavek_shape_key(w);
-            if (!w.use || w.waves != 4 || w.depth != 2 || w.tail_tiles > 0 || w.partial_bytes > p.ws.partial_bytes ||
-                !((key == 1142 && (it.enc->wavek_spread & 2)) || key == 142 || (key == 242 && (it.enc->wavek_spread & 1)))) { dense_grouped = false; break; }
-            if (key0 < 0) key0 = key;
-            if (key != key0) { dense_grouped = false; break; }
+            if (!wavek_multi_instantiated(it.enc, w) || w.tail_tiles > 0 || w.partial_bytes > p.ws.partial_bytes) { dense_grouped = false; break; }
+            if (key0 < 0) key0 = wavek_shape_key(w);
+            if (wavek_shape_key(w) != key0) { dense_grouped = false; break; }
             unsigned long long* tickets = reinterpret_cast<unsigned long long*>(base + p.enc_off + p.ws.ticket_off) + nl * kLayerTicketWords;
-            m.item[k] = wavek_args(it.enc, D, w, reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[nl - 1]), p.n, z_out + (size_t)p.row0 * J,
-                                   reinterpret_cast<float*>(base + p.enc_off + p.ws.partial_off), tickets, nonce, 0);
-            m.item[k].timeline = nullptr;
-            m.nblk[k] = w.blocks();
-            m.range.first[k] = at;
-            at += (w.blocks() + 7) / 8 * 8;
+            wavek_multi_append(m, at, wavek_args(it.enc, D, w, reinterpret_cast<const float*>(base + p.enc_off + p.ws.act_off[nl - 1]), p.n, z_out + (size_t)p.row0 * J,
+                                                 reinterpret_cast<float*>(base + p.enc_off + p.ws.partial_off), tickets, nonce, 0), w);
         }
+        dense_grouped = dense_grouped && launch_wavek_multi(key0, m, 0, at, stream, nullptr);      // (no instantiation: the per-object path below)
         if (dense_grouped) {
-            m.range.first[members.size()] = at;
-            m.xcd_affine = 0;
-            switch (key0) {
-                case 1142: launch_wavek_multi_t<1, 1, true>(m, 0, at, stream); break;
-                case 142: launch_wavek_multi_t<2, 1, false>(m, 0, at, stream); break;
-                case 242: launch_wavek_multi_t<2, 2, true>(m, 0, at, stream); break;
-                default: dense_grouped = false;
-            }
-            if (dense_grouped) {
-                AAE_HIP_TRY(hipGetLastError());
-                ++t_multi_launches;
-            }
+            AAE_HIP_TRY(hipGetLastError());
+            ++t_multi_launches;
         }
     }
     if (!dense_grouped)
@@ -962,6 +920,33 @@ static bool expand_items(const aae_multi_item* items, int n_items, bool scan_onl
     return true;
 }
 
+// the members of a group read their crops from one [rows, H, W, C] array
+static int check_crop_shapes(const aae_multi_item* items, const std::vector<int>& g) {
+    for (int i : g) {
+        const aae_encoder_desc &a = items[i].enc->desc, &b = items[g[0]].enc->desc;
+        if (a.in_h != b.in_h || a.in_w != b.in_w || a.in_c != b.in_c) return fail(AAE_ERR_RUNTIME, "multi-object query: group members differ in crop shape");
+    }
+    return AAE_OK;
+}
+
+// Winograd-domain weights (+83.5 MB for the reference network) for the objects of a frame that will run a layer in that form, and only for them (an estimator with thirty
+// classes of a few boxes each never builds them): an object whose OWN forward at its count takes the form (as aae_encoder_workspace_bytes does), and the members of every
+// per-detection group with a Winograd layer and of every mid-batch group that ONE plan made as if all weights were there says would form.  Not from a hot call: it allocates.
+static int prepare_winograd_for_frame(const aae_multi_item* items, int n_items) {
+    for (int i = 0; items && i < n_items; ++i)
+        if (items[i].enc && items[i].n >= 1 && wants_winograd_weights(items[i].enc, items[i].n))
+            if (int rc = ensure_winograd_weights(items[i].enc)) return rc;
+    MultiPlan dry;
+    if (int rc = plan_multi(items, n_items, false, dry, true)) return rc;
+    std::vector<int> members;
+    for (size_t gi = 0; gi < dry.groups.size(); ++gi)
+        if (std::find(dry.group_wino[gi].begin(), dry.group_wino[gi].end(), 1) != dry.group_wino[gi].end()) members.insert(members.end(), dry.groups[gi].begin(), dry.groups[gi].end());
+    for (const std::vector<int>& g : dry.mid_groups) members.insert(members.end(), g.begin(), g.end());
+    for (int i : members)
+        if (int rc = ensure_winograd_weights(items[i].enc)) return rc;
+    return AAE_OK;
+}
+
 static int multi_impl(const aae_multi_item* items_in, int n_items_in, const void* x, int x_dtype, const float* z_in, float* z_out, int64_t* idx_out,
                       float* score_out, void* workspace, size_t ws_bytes, void* stream_v) {
     const bool scan_only = z_in != nullptr;
@@ -1002,10 +987,7 @@ static int multi_impl(const aae_multi_item* items_in, int n_items_in, const void
     // ---- mid-batch groups: one Winograd launch per conv layer and group
     for (size_t gi = 0; gi < mp.mid_groups.size(); ++gi) {
         const std::vector<int>& g = mp.mid_groups[gi];
-        for (int i : g) {
-            const aae_encoder_desc &a = items[i].enc->desc, &b = items[g[0]].enc->desc;
-            if (a.in_h != b.in_h || a.in_w != b.in_w || a.in_c != b.in_c) return fail(AAE_ERR_RUNTIME, "multi-object query: group members differ in crop shape");
-        }
+        if (int rc = check_crop_shapes(items, g)) return rc;
         static const std::vector<char> none;
         if (int rc = launch_mid_group(items, mp, g, gi < mp.mid_wino.size() ? mp.mid_wino[gi] : none, gi < mp.mid_rem.size() ? mp.mid_rem[gi] : none, x, x_dtype, z_out, idx_out,
                                       score_out, base, stream_v)) return rc;
@@ -1016,10 +998,7 @@ static int multi_impl(const aae_multi_item* items_in, int n_items_in, const void
         const std::vector<int>& g = mp.groups[gidx];
         const unsigned nonce = next_nonce();           // one per group and call: every ticketed launch has its own words
         if (!scan_only) {
-            for (int i : g) {
-                const aae_encoder_desc &a = items[i].enc->desc, &b = items[g[0]].enc->desc;
-                if (a.in_h != b.in_h || a.in_w != b.in_w || a.in_c != b.in_c) return fail(AAE_ERR_RUNTIME, "multi-object query: group members differ in crop shape");
-            }
+            if (int rc = check_crop_shapes(items, g)) return rc;
             static const std::vector<char> no_wino;
             if (int rc = launch_encoder_multi(items, mp, g, gidx < mp.group_wino.size() ? mp.group_wino[gidx] : no_wino, x, x_dtype, z_out, base, nonce, stream)) return rc;
         }
@@ -1037,36 +1016,8 @@ size_t aae_multi_workspace_bytes(const aae_multi_item* items_in, int n_items_in,
     const bool split = aae_host::expand_items(items_in, n_items_in, scan_only != 0, expanded);
     const aae_multi_item* items = split ? expanded.data() : items_in;
     const int n_items = split ? (int)expanded.size() : n_items_in;
-    // (the one place outside the hot calls that sees a frame's layout: objects that may join a mid-batch group get their Winograd weights here)
-    // Winograd-domain weights (+83.5 MB for the reference network) only for the objects of a group that WOULD form (an estimator with thirty classes of a few boxes each never builds them).
-    if (items && !scan_only) {
-        for (int i = 0; i < n_items; ++i)          // (an object whose OWN forward at this count takes the Winograd form: as aae_encoder_workspace_bytes does)
-            if (items[i].enc && items[i].n >= 1 && aae_host::wants_winograd_weights(items[i].enc, items[i].n) && aae_host::ensure_winograd_weights(items[i].enc) != AAE_OK) return 0;
-        {   // per-detection groups with a layer in the Winograd form (multi_group_winograd): a dry plan tells which
-            aae_host::MultiPlan dry;
-            if (aae_host::plan_multi(items, n_items, false, dry, true) != AAE_OK) return 0;
-            for (size_t gi = 0; gi < dry.groups.size(); ++gi) {
-                bool any = false;
-                for (char c : dry.group_wino[gi]) any = any || c;
-                if (any)
-                    for (int k : dry.groups[gi])
-                        if (aae_host::ensure_winograd_weights(items[k].enc) != AAE_OK) return 0;
-            }
-        }
-        std::vector<std::vector<int>> sigs((size_t)n_items);
-        std::vector<char> cand((size_t)n_items, 0), seen((size_t)n_items, 0);
-        for (int i = 0; i < n_items; ++i)
-            cand[(size_t)i] = items[i].enc && items[i].cb && items[i].n >= 5 && aae_host::multi_encoder_mid_groupable(items[i].enc, items[i].n, sigs[(size_t)i], true);
-        for (int i = 0; i < n_items; ++i) {
-            if (!cand[(size_t)i] || seen[(size_t)i]) continue;
-            std::vector<int> members, counts;
-            for (int k = i; k < n_items && (int)members.size() < aae::kMultiMax; ++k)
-                if (cand[(size_t)k] && !seen[(size_t)k] && sigs[(size_t)k] == sigs[(size_t)i]) { members.push_back(k); counts.push_back(items[k].n); seen[(size_t)k] = 1; }
-            if (members.size() >= 2 && aae_host::mid_group_fills(items[members[0]].enc, counts))
-                for (int k : members)
-                    if (aae_host::ensure_winograd_weights(items[k].enc) != AAE_OK) return 0;
-        }
-    }
+    // (the one place outside the hot calls that sees a frame's layout)
+    if (!scan_only && aae_host::prepare_winograd_for_frame(items, n_items) != AAE_OK) return 0;
     aae_host::MultiPlan mp;
     if (aae_host::plan_multi(items, n_items, scan_only != 0, mp) != AAE_OK) return 0;
     return mp.total;
