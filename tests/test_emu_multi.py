@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import emu_backend as eb
+import multi_form_cases as mfc
 from augmentedautoencoder_amd import _lib
 from augmentedautoencoder_amd.weights import EncoderConfig
 from oracle import reference_cpu as ref
@@ -292,7 +293,13 @@ def test_argument_errors_are_reported_not_crashed():
     _close([a, b])
 
 
-_WINO = {'winograd_min_batch': 1, 'winograd_min_blocks': 1, 'first_group_split_max_tiles': 0}      # (every eligible layer as Winograd, alone and in a group: the emulated launches are tiny against the 256 compute units the fill rule counts with; conv1 in its whole-tile form, as at the batch sizes that group on the GPU)
+def _case_objects(case):
+    """the objects of a case of tests/multi_form_cases.py (shared with the hardware twins, tests/test_gpu_multi_forms.py): (cfg, counts, [(encoder, codebook, weights)])"""
+    c = mfc.CASES[case]
+    cfg = mfc.config(case)
+    return cfg, c['counts'], [_object(cfg, seed, rows, c['options']) for seed, rows in zip(c['weight_seeds'], c['codebook_rows'])]
+
+
 
 
 @pytest.mark.parametrize('order', [0, 2])
@@ -300,17 +307,16 @@ def test_per_detection_group_runs_conv_layers_as_one_winograd_launch_where_the_g
     """three objects with 1, 2 and 4 detections (a frame of a detector): with the block-count rule forced low the group's conv2 (16 x 16-pixel regions) and conv3 (four 8 x 8 images per
     block: every object one ragged block) run as ONE Winograd launch each across the objects (multi_group_winograd) between the grouped conv1 and the GEMV / scan launches.  The conv
     layers are the objects' own Winograd launches bit for bit; latents against the per-object calls within the group plan's summation order, and right against the oracle."""
-    cfg = EncoderConfig((64, 64, 3), [32, 64, 64], [2, 2, 2], 5, 128, True)
-    counts = [1, 2, 4]
-    opts = {'winograd_min_batch': 1, 'winograd_min_blocks': 1}
+    case = 'per_detection_group_winograd'
+    want = mfc.CASES[case]['launches']
     eb.set_block_order(order)
     try:
-        objs = [_object(cfg, 950 + 7 * o, 36 * (8 + o) + o, opts) for o in range(3)]
+        cfg, counts, objs = _case_objects(case)
         items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
-        x = synth.make_crops(sum(counts), seed=63, shape=cfg.shape)
+        x = mfc.crops(case)
         z0, i0, s0 = _per_object(items, x)                               # (every object's own call: Winograd conv layers too under these options)
         z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-        assert launches == 5                                             # conv1, conv2 (Winograd), conv3 (Winograd), GEMV, scan
+        assert launches == want['default'] == 5                          # conv1, conv2 (Winograd), conv3 (Winograd), GEMV, scan
         assert np.abs(z1 - z0).max() / np.abs(z0).max() < 2e-6 and np.array_equal(i1, i0)
         at = 0
         for (e, c, w), n in zip(objs, counts):
@@ -321,7 +327,7 @@ def test_per_detection_group_runs_conv_layers_as_one_winograd_launch_where_the_g
         for e, _, _ in objs:
             e.set_option('multi_group_winograd', 0)                      # the wave-split-K kernel for every conv layer again
         z2, i2, s2, launches = eb.encode_nn_multi(items, x)
-        assert launches == 5 and np.abs(z2 - z0).max() / np.abs(z0).max() < 5e-6 and np.array_equal(i2, i0)
+        assert launches == want['multi_group_winograd=0'] == 5 and np.abs(z2 - z0).max() / np.abs(z0).max() < 5e-6 and np.array_equal(i2, i0)
         assert not np.array_equal(z2, z1)                                # (another kernel computed the conv layers)
         _close(objs)
     finally:
@@ -333,16 +339,15 @@ def test_mid_batch_group_one_winograd_launch_per_conv_layer_across_objects(order
     """objects with 5 or more detections each: ONE launch per layer across the objects -- conv1, the dense layer where the members' plans agree, the scans, ONE Winograd launch per conv layer across
     the objects (conv_wino_layer_multi_kernel) -- both block geometries (16 x 16-pixel regions of one image; four 8 x 8 images per block,
     ragged groups), three objects with different detection counts; bit for bit the per-object calls, and right against the oracle."""
-    cfg = EncoderConfig((64, 64, 3), [32, 64, 64], [2, 2, 2], 5, 128, True)
-    counts = [5, 7, 6]
+    case = 'mid_batch_group'
     eb.set_block_order(order)
     try:
-        objs = [_object(cfg, 500 + 7 * o, 36 * (9 + 2 * o) + 3 * o, _WINO) for o in range(3)]
+        cfg, counts, objs = _case_objects(case)
         items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
-        x = synth.make_crops(sum(counts), seed=58, shape=cfg.shape)
+        x = mfc.crops(case)
         z0, i0, s0 = _per_object(items, x)
         z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-        assert launches == 5                                             # (the grouped launches: conv1 in its whole-tile form, conv2, conv3, the three scans as one launch + one reduce launch; the dense GEMV per object)
+        assert launches == mfc.CASES[case]['launches']['default'] == 5   # (the grouped launches: conv1 in its whole-tile form, conv2, conv3, the three scans as one launch + one reduce launch; the dense GEMV per object)
         assert np.array_equal(z1, z0) and np.array_equal(i1, i0) and np.array_equal(s1, s0)
         at = 0
         for (e, c, w), n in zip(objs, counts):
@@ -352,10 +357,12 @@ def test_mid_batch_group_one_winograd_launch_per_conv_layer_across_objects(order
             assert np.array_equal(i1[at:at + n], np.argmax(cs, axis=1))
             at += n
         # a frame that mixes a per-detection group (n <= 4), a mid-batch group and a loner that joins neither (its own options)
-        lone = _object(cfg, 600, 36 * 8, dict(_WINO, multi_mid_group=0))
-        small = [_object(cfg, 610 + o, 36 * 7 + o) for o in range(2)]
-        mixed = [(small[0][0], small[0][1], 2, 1)] + items[:2] + [(lone[0], lone[1], 5, 1), (small[1][0], small[1][1], 1, 1)]
-        xm = synth.make_crops(sum(it[2] for it in mixed), seed=59, shape=cfg.shape)
+        mx = mfc.CASES[case]['mixed']
+        lone = _object(cfg, mx['lone_seed'], mx['lone_rows'], mx['lone_options'])
+        small = [_object(cfg, seed, rows, mx['small_options']) for seed, rows in zip(mx['small_seeds'], mx['small_rows'])]
+        mixed = ([(small[0][0], small[0][1], mx['small_counts'][0], 1)] + items[:2] + [(lone[0], lone[1], mx['lone_count'], 1),
+                 (small[1][0], small[1][1], mx['small_counts'][1], 1)])
+        xm = mfc.crops(case, seed=mx['crop_seed'], rows=sum(it[2] for it in mixed))
         zp, ip, sp = _per_object(mixed, xm)
         zm, im, sm, _ = eb.encode_nn_multi(mixed, xm)
         assert np.array_equal(im, ip)
@@ -375,17 +382,16 @@ def test_mid_batch_group_hands_incomplete_four_image_blocks_to_one_wave_split_k_
     """conv3 of this net packs four 8 x 8 images per block: counts {5, 7, 6} = 6 blocks, 3 of them incomplete.  On a "chip" of 4 compute units the
     incomplete ones open a second round: the objects' last 1 / 3 / 2 images go to ONE grouped wave-split-K launch (plan_mid_ragged) -- the same
     answers up to fp32 summation order on those images, bit for bit on the others; option multi_mid_ragged = 0 keeps every image in the Winograd launch."""
-    cfg = EncoderConfig((64, 64, 3), [32, 64, 64], [2, 2, 2], 5, 128, True)
-    counts = [5, 7, 6]
-    opts = dict(_WINO, wavek_target_blocks=4, winograd_xcd_cols=0)
+    case = 'mid_batch_group_ragged'
+    want = mfc.CASES[case]['launches']
     eb.set_block_order(order)
     try:
-        objs = [_object(cfg, 800 + 7 * o, 36 * (9 + 2 * o) + 3 * o, opts) for o in range(3)]
+        cfg, counts, objs = _case_objects(case)
         items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
-        x = synth.make_crops(sum(counts), seed=61, shape=cfg.shape)
+        x = mfc.crops(case)
         z0, i0, s0 = _per_object(items, x)
         z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-        assert launches == 6                                             # conv1, conv2, conv3's complete blocks, conv3's last images, scans, reduce
+        assert launches == want['default'] == 6                          # conv1, conv2, conv3's complete blocks, conv3's last images, scans, reduce
         at = 0
         for (e, c, w), n in zip(objs, counts):
             full = n // 4 * 4
@@ -399,11 +405,11 @@ def test_mid_batch_group_hands_incomplete_four_image_blocks_to_one_wave_split_k_
         for e, _, _ in objs:
             e.set_option('multi_mid_ragged', 0)
         z2, i2, s2, launches = eb.encode_nn_multi(items, x)
-        assert launches == 5 and np.array_equal(z2, z0) and np.array_equal(i2, i0) and np.array_equal(s2, s0)
+        assert launches == want['multi_mid_ragged=0'] == 5 and np.array_equal(z2, z0) and np.array_equal(i2, i0) and np.array_equal(s2, s0)
         for e, _, _ in objs:
             e.set_option('multi_mid_scan', 0)
         z3, i3, s3, launches = eb.encode_nn_multi(items, x)                # (the scans per object again: the same answers from two launches fewer in the count)
-        assert launches == 3 and np.array_equal(z3, z0) and np.array_equal(i3, i0) and np.array_equal(s3, s0)
+        assert launches == want['multi_mid_ragged=0,multi_mid_scan=0'] == 3 and np.array_equal(z3, z0) and np.array_equal(i3, i0) and np.array_equal(s3, s0)
         _close(objs)
     finally:
         eb.set_block_order(0)
@@ -412,15 +418,14 @@ def test_mid_batch_group_hands_incomplete_four_image_blocks_to_one_wave_split_k_
 def test_mid_batch_fill_rule_counts_the_complete_blocks_when_the_incomplete_ones_leave():
     """Two objects with 25 + 24 crops on a "chip" of 12 compute units, conv2 with four 8 x 8 images per block: 13 blocks would occupy two rounds at 54 % (below the 56 % of
     the fill rule: no group); handing the one incomplete block's image to the wave-split-K launch leaves 12 blocks = one full round: the group forms."""
-    cfg = EncoderConfig((32, 32, 3), [32, 64], [2, 2], 5, 128)
-    counts = [25, 24]
-    opts = {'winograd_min_batch': 1, 'first_group_split_max_tiles': 0, 'wavek_target_blocks': 12, 'winograd_xcd_cols': 0}
-    objs = [_object(cfg, 900 + o, 36 * 8 + o, opts) for o in range(2)]
+    case = 'mid_batch_fill_rule'
+    want = mfc.CASES[case]['launches']
+    cfg, counts, objs = _case_objects(case)
     items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
-    x = synth.make_crops(sum(counts), seed=62, shape=cfg.shape)
+    x = mfc.crops(case)
     z0, i0, s0 = _per_object(items, x)
     z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-    assert launches == 6                                                 # conv1, conv2's twelve complete blocks, the 25th crop of object 0, the dense layer, scans, reduce
+    assert launches == want['default'] == 6                              # conv1, conv2's twelve complete blocks, the 25th crop of object 0, the dense layer, scans, reduce
     assert np.abs(z1 - z0).max() / np.abs(z0).max() < 5e-6
     at = 0
     for (e, c, w), n in zip(objs, counts):
@@ -431,7 +436,7 @@ def test_mid_batch_fill_rule_counts_the_complete_blocks_when_the_incomplete_ones
     for e, _, _ in objs:
         e.set_option('multi_mid_ragged', 0)
     z2, i2, s2, launches = eb.encode_nn_multi(items, x)
-    assert launches == 0 and np.array_equal(z2, z0) and np.array_equal(i2, i0)          # (13 blocks in two rounds: below the rule, one object after the other)
+    assert launches == want['multi_mid_ragged=0'] == 0 and np.array_equal(z2, z0) and np.array_equal(i2, i0)          # (13 blocks in two rounds: below the rule, one object after the other)
     _close(objs)
 
 
@@ -439,14 +444,14 @@ def test_mid_batch_group_takes_the_layers_it_fills_and_leaves_the_others_to_the_
     """two classes with six boxes each on a "chip" of 8 compute units: conv2 (one 16 x 16-pixel region per box: 12 blocks, two rounds at 75 %) runs as ONE Winograd launch across
     the objects, conv3 (four 8 x 8 images per block: 4 blocks, half a round) does not pass the rule and runs per object on the kernel the object's own forward takes -- here
     bit for bit the per-object calls (their conv2 passes the rule alone too)."""
-    cfg = EncoderConfig((64, 64, 3), [32, 64, 64], [2, 2, 2], 5, 128, True)
-    opts = {'winograd_min_batch': 1, 'first_group_split_max_tiles': 0, 'wavek_target_blocks': 8, 'winograd_xcd_cols': 0}
-    objs = [_object(cfg, 970 + o, 36 * 8 + o, opts) for o in range(2)]
-    items = [(e, c, 6, 1) for e, c, _ in objs]
-    x = synth.make_crops(12, seed=64, shape=cfg.shape)
+    case = 'mid_batch_group_some_layers'
+    cfg, counts, objs = _case_objects(case)
+    assert counts == [6, 6]
+    items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
+    x = mfc.crops(case)
     z0, i0, s0 = _per_object(items, x)
     z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-    assert launches == 4                                                 # conv1, conv2, the scans, the reduce (conv3 and the dense GEMV per object)
+    assert launches == mfc.CASES[case]['launches']['default'] == 4       # conv1, conv2, the scans, the reduce (conv3 and the dense GEMV per object)
     assert np.array_equal(z1, z0) and np.array_equal(i1, i0) and np.array_equal(s1, s0)
     for k, (e, c, w) in enumerate(objs):
         z64 = ref.encoder_forward_np(ref.input_to_float(x[6 * k:6 * k + 6]), w, cfg.strides, cfg.batch_norm)
@@ -458,14 +463,14 @@ def test_a_class_with_a_few_boxes_beyond_four_joins_the_per_detection_group_as_i
     """a frame with 6 boxes of one class and 2 of another: the library answers the first class as two items (4 + 2 boxes, the same handles) inside the frame's per-detection
     group -- six launches for the frame; answers within the group plan's summation order of the per-class calls and right against the oracle.  multi_split_items = 0: the
     6-box class takes its own call."""
-    cfg = EncoderConfig((16, 16, 3), [32, 64, 64, 32], [2, 2, 2, 1], 5, 128, True)
-    objs = [_object(cfg, 980 + o, 36 * 9 + o) for o in range(2)]
-    counts = [6, 2]
+    case = 'split_items'
+    cfg, counts, objs = _case_objects(case)
+    assert counts == [6, 2]
     items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
-    x = synth.make_crops(8, seed=65, shape=cfg.shape)
+    x = mfc.crops(case)
     z0, i0, s0 = _per_object(items, x)
     z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-    assert launches == 6                                                 # conv1, three conv layers, GEMV, scan: one group of three items
+    assert launches == mfc.CASES[case]['launches']['default'] == 6       # conv1, three conv layers, GEMV, scan: one group of three items
     assert np.abs(z1 - z0).max() / np.abs(z0).max() < 5e-6 and np.array_equal(i1, i0) and np.abs(s1 - s0).max() < 1e-6
     at = 0
     for (e, c, w), n in zip(objs, counts):
@@ -481,11 +486,12 @@ def test_a_class_with_a_few_boxes_beyond_four_joins_the_per_detection_group_as_i
 
 
 def test_mid_batch_group_needs_two_members_that_fill_the_chip():
-    cfg = EncoderConfig((64, 64, 3), [32, 64, 64], [2, 2, 2], 5, 128, True)
-    objs = [_object(cfg, 700 + o, 36 * 8, {'winograd_min_batch': 1, 'multi_split_items': 0}) for o in range(2)]            # default fill rule: two tiny launches do not fill 256 compute units
-    items = [(e, c, 5, 1) for e, c, _ in objs]
-    x = synth.make_crops(10, seed=60, shape=cfg.shape)
+    case = 'no_group'
+    cfg, counts, objs = _case_objects(case)                              # default fill rule: two tiny launches do not fill 256 compute units
+    assert counts == [5, 5]
+    items = [(e, c, n, 1) for (e, c, _), n in zip(objs, counts)]
+    x = mfc.crops(case)
     z0, i0, s0 = _per_object(items, x)
     z1, i1, s1, launches = eb.encode_nn_multi(items, x)
-    assert launches == 0 and np.array_equal(z1, z0) and np.array_equal(i1, i0)
+    assert launches == mfc.CASES[case]['launches']['default'] == 0 and np.array_equal(z1, z0) and np.array_equal(i1, i0)
     _close(objs)
