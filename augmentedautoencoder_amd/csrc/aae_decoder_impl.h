@@ -119,30 +119,23 @@ static int launch_stage(aae_decoder* dec, const DecStage& s, const float* x, int
     aae_encoder* ctx = &dec->ctx;
     const Layer& L = s.L;
     const double flops = s.nominal_flops_per_image * B;
-    char label[128];
     if (s.mode == STAGE_IGEMM_PLAIN) return launch_igemm(ctx, L, x, B * s.UH * s.UW, out, partial, stream, tm, name);
     if (s.mode == STAGE_IGEMM_PHASED) {
+        // every output phase is a stride-1 convolution of the stage's INPUT grid with a U x U kernel of its own (padding per phase, below)
+        Layer P = L;
+        P.Ho = L.H; P.Wo = L.W; P.KS = s.U; P.S = 1; P.pt = 0; P.pl = 0; P.relu = (s.act == aae::ACT_RELU);
         aae::ConvIgemmArgs a;
-        a.x = x; a.wp = s.wp_phases; a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift; a.out = out;
-        a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Ho = L.H; a.Wo = L.W; a.Cout = L.Cout; a.CoutPad = L.CoutPad;
-        a.KS = s.U; a.S = 1; a.pt = 0; a.pl = 0; a.M = B * L.H * L.W; a.relu = (s.act == aae::ACT_RELU); a.stagger = 0;
-        const unsigned long long x_bytes = (unsigned long long)B * L.H * L.W * L.Cin * sizeof(float);
-        if (x_bytes >= 0xFFFFFFF0ull) return fail(AAE_ERR_UNSUPPORTED, "%s: activation of %llu bytes exceeds the 4 GiB buffer view", name, x_bytes);
-        a.x_bytes = (unsigned)x_bytes;
-        a.slabs_total = s.U * s.U * L.Cin / 32;
+        a.x = x; a.wp = s.wp_phases; a.out = out; a.stagger = 0;
+        if (int rc = conv_layer_args(a, P, B * L.H * L.W, name)) return rc;
         a.slabs_per_split = a.slabs_total;
-        a.wp_bytes = (unsigned)((unsigned long long)a.slabs_total * 8ull * L.CoutPad * 16ull);
         a.wp_phase_floats = s.wp_phase_floats;
         a.ph_pt[0] = s.ph_pt[0]; a.ph_pt[1] = s.ph_pt[1]; a.ph_pl[0] = s.ph_pt[0]; a.ph_pl[1] = s.ph_pt[1];
         a.num_mt = ceil_div(a.M, 128);
         a.num_nt = L.CoutPad / 128;
         a.splits = 4;                              // the four output phases
-        const int nblk = a.num_mt * a.num_nt * 4;
-        AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, true>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        snprintf(label, sizeof(label), "%s:upconv2x_igemm_f32_dma 4 phases x (M=%d N=%d K=%d)", name, a.M, L.Cout, s.U * s.U * L.Cin);
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
+        if (!launch_igemm_form(IGEMM_UPCONV_PHASES, true, 0, dim3(a.num_mt * a.num_nt * 4), aae::kConvIgemmSmem, stream, a))
+            return fail(AAE_ERR_RUNTIME, "%s: no phase-folded igemm instantiation in this build", name);
+        return launch_done(tm, flops, "%s:upconv2x_igemm_f32_dma 4 phases x (M=%d N=%d K=%d)", name, a.M, L.Cout, s.U * s.U * L.Cin);
     }
     if (s.mode == STAGE_NARROW_PHASED) {
         aae::UpconvNarrowArgs a;
@@ -151,12 +144,10 @@ static int launch_stage(aae_decoder* dec, const DecStage& s, const float* x, int
         a.tiles_y = ceil_div(L.H, 16); a.tiles_x = ceil_div(L.W, 16);
         a.row_stride = aae::narrow_row_stride(s.Un);
         const int smem = aae::narrow_smem_bytes(s.Un);
+        // (one kernel, no form list; its LDS size depends on the stage's tap count, so the ceiling follows the stage that is launched -- once per decode, not on the per-detection path)
         (void)hipFuncSetAttribute((const void*)aae::upconv2x_narrow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         AAE_LAUNCH((aae::upconv2x_narrow_kernel), dim3((unsigned)(B * a.tiles_y * a.tiles_x)), dim3(256), smem, stream, a);
-        snprintf(label, sizeof(label), "%s:upconv2x_narrow px=%lld Cin=%d Cout=%d taps=%dx%d", name, (long long)B * L.H * L.W, L.Cin, L.Cout, s.Un, s.Un);
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
+        return launch_done(tm, flops, "%s:upconv2x_narrow px=%lld Cin=%d Cout=%d taps=%dx%d", name, (long long)B * L.H * L.W, L.Cin, L.Cout, s.Un, s.Un);
     }
     aae::UpconvDirectArgs a;
     a.x = x; a.w = L.w_hwio; a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift; a.out = out;
@@ -165,10 +156,7 @@ static int launch_stage(aae_decoder* dec, const DecStage& s, const float* x, int
     long long blocks = (a.total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     AAE_LAUNCH((aae::upconv_direct_kernel), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    snprintf(label, sizeof(label), "%s:upconv_direct", name);
-    note_kernel({label, flops});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    return launch_done(tm, flops, "%s:upconv_direct", name);
 }
 
 static int decoder_forward_impl(aae_decoder* dec, const float* z, int B, float* x_out, void* workspace, size_t ws_bytes,
@@ -335,11 +323,7 @@ int aae_decoder_create(const aae_decoder_desc* d, const void* const* hw, int n_w
         dec->stages.push_back(s);
         H = s.UH; W = s.UW; C = Ls.Cout;
     }
-    (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
-    (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
-    (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
-    (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
-    (void)hipFuncSetAttribute((const void*)aae::conv_igemm_f32_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kConvIgemmSmem);
+    set_launch_attributes(ctx);
     *out = dec;
     return AAE_OK;
 }

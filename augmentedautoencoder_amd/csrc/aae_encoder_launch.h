@@ -20,18 +20,227 @@ struct Timer {
     }
 };
 
-static int launch_igemm(aae_encoder* enc, const Layer& L, const float* x, int M, float* out, float* partial,
-                        hipStream_t stream, Timer& tm, const char* name, int tag = 0) {
-    aae::ConvIgemmArgs a;
-    a.x = x; a.wp = L.wp; a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift;
+// The end of every launch function: the kernel's record under its printf-style label, the launch's error, the timer's event.
+__attribute__((format(printf, 3, 4))) static int launch_done(Timer& tm, double flops, const char* fmt, ...) {
+    char label[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(label, sizeof(label), fmt, ap);
+    va_end(ap);
+    note_kernel({label, flops});
+    AAE_HIP_TRY(hipGetLastError());
+    return tm.mark();
+}
+
+// ------------------------------------------------------------ form lists
+// Every instantiation of a kernel family is ONE row of the family's list, X(when, kernel, lds): `when` selects the row from the family's dispatch keys (a form has
+// exactly the layer tags its rows name: a tag only makes the symbol unique per encoder layer -- separate rows in rocprofv3 --stats -- and a list never instantiates
+// one the launch code does not ask for), `kernel` is the instantiation in parentheses, `lds` the most dynamic LDS it is launched with.  Two things are generated from
+// a list, and from nothing else: the family's dispatch -- AAE_FORM_LAUNCH in a function whose parameters are the keys, false for "no such form in this build" -- and
+// the family's line in set_launch_attributes, which raises the LDS ceiling of every row when a handle is created.  A new or retired form is one row.  The rows of
+// the experiments build sit in the *_EXPERIMENTS part of their list.
+#define AAE_FORM_LAUNCH(when, kernel, lds) if (when) { AAE_LAUNCH(kernel, grid, block, lds, stream, a); return true; }
+// (a launch below the row's ceiling: `smem` of the enclosing function -- a size that depends on the layer or on the grid)
+#define AAE_FORM_LAUNCH_SMEM(when, kernel, lds) if (when) { AAE_LAUNCH(kernel, grid, block, smem, stream, a); return true; }
+#define AAE_FORM_CEILING(when, kernel, lds) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+
+// conv_igemm_f32_kernel<SPLITK, DMA, SCATTER, TAG, BREG, NW>, encoder and decoder.  The register-staged operand path (!dma) and LDS-DMA without the weights in
+// registers on a tagged layer are reachable in the experiments build only.
+enum IgemmForm { IGEMM_PLAIN, IGEMM_BREG, IGEMM_BREG_N256, IGEMM_SPLITK, IGEMM_UPCONV_PHASES };
+#ifdef AAE_EXPERIMENTS
+#define AAE_IGEMM_FORMS_EXPERIMENTS(X) \
+    X(form == IGEMM_PLAIN && dma && tag == 1, (aae::conv_igemm_f32_kernel<false, true, false, 1>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_PLAIN && dma && tag == 2, (aae::conv_igemm_f32_kernel<false, true, false, 2>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_PLAIN && dma && tag == 3, (aae::conv_igemm_f32_kernel<false, true, false, 3>), aae::kConvIgemmSmem)
+#else
+#define AAE_IGEMM_FORMS_EXPERIMENTS(X)
+#endif
+#define AAE_IGEMM_FORMS(X) \
+    X(form == IGEMM_BREG_N256 && tag == 1, (aae::conv_igemm_f32_kernel<false, true, false, 1, true, 4>), 2 * aae::kSlabFloatsA * 4) \
+    X(form == IGEMM_BREG_N256 && tag == 2, (aae::conv_igemm_f32_kernel<false, true, false, 2, true, 4>), 2 * aae::kSlabFloatsA * 4) \
+    X(form == IGEMM_BREG && tag == 1, (aae::conv_igemm_f32_kernel<false, true, false, 1, true>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_BREG && tag == 2, (aae::conv_igemm_f32_kernel<false, true, false, 2, true>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_BREG && tag == 3, (aae::conv_igemm_f32_kernel<false, true, false, 3, true>), aae::kConvIgemmSmem) \
+    AAE_IGEMM_FORMS_EXPERIMENTS(X) \
+    X(form == IGEMM_PLAIN && dma, (aae::conv_igemm_f32_kernel<false, true>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_PLAIN && !dma, (aae::conv_igemm_f32_kernel<false>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_SPLITK && dma, (aae::conv_igemm_f32_kernel<true, true>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_SPLITK && !dma, (aae::conv_igemm_f32_kernel<true>), aae::kConvIgemmSmem) \
+    X(form == IGEMM_UPCONV_PHASES, (aae::conv_igemm_f32_kernel<false, true, true>), aae::kConvIgemmSmem)
+
+// conv_igemm_x3h_kernel<OUT> (register-staged), conv_igemm_x3h_dma_kernel<OUT, TAG, WM> and conv_igemm_x3h_wide_kernel<OUT, TAG>
+enum X3hForm { X3H_PLANES, X3H_F32, X3H_PARTIAL, X3H_WIDE256, X3H_WIDE128 };
+#ifdef AAE_EXPERIMENTS
+#define AAE_X3H_FORMS_EXPERIMENTS(X) \
+    X(form == X3H_WIDE128 && tag == 1, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 1, 4>), (aae::x3h_dma_smem<4>())) \
+    X(form == X3H_WIDE128 && tag == 2, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 2, 4>), (aae::x3h_dma_smem<4>())) \
+    X(form == X3H_WIDE128 && tag == 3, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 3, 4>), (aae::x3h_dma_smem<4>())) \
+    X(form == X3H_F32 && !dma, (aae::conv_igemm_x3h_kernel<aae::X3H_OUT_F32>), aae::kConvIgemmSmem) \
+    X(form == X3H_PLANES && !dma, (aae::conv_igemm_x3h_kernel<aae::X3H_OUT_PLANES>), aae::kConvIgemmSmem) \
+    X(form == X3H_PARTIAL && !dma, (aae::conv_igemm_x3h_kernel<aae::X3H_OUT_PARTIAL>), aae::kConvIgemmSmem)
+#else
+#define AAE_X3H_FORMS_EXPERIMENTS(X)
+#endif
+#define AAE_X3H_FORMS(X) \
+    X(form == X3H_WIDE256 && tag == 1, (aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 1>), aae::kX3hWideSmem) \
+    X(form == X3H_WIDE256 && tag == 2, (aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 2>), aae::kX3hWideSmem) \
+    X(form == X3H_WIDE256 && tag == 3, (aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 3>), aae::kX3hWideSmem) \
+    AAE_X3H_FORMS_EXPERIMENTS(X) \
+    X(form == X3H_F32 && dma, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_F32>), aae::kConvIgemmSmem) \
+    X(form == X3H_PLANES && dma && tag == 1, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 1>), aae::kConvIgemmSmem) \
+    X(form == X3H_PLANES && dma && tag == 2, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 2>), aae::kConvIgemmSmem) \
+    X(form == X3H_PLANES && dma && tag == 3, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 3>), aae::kConvIgemmSmem) \
+    X(form == X3H_PLANES && dma, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES>), aae::kConvIgemmSmem) \
+    X(form == X3H_PARTIAL && dma, (aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PARTIAL>), aae::kConvIgemmSmem)
+
+// conv_wavek_f32_kernel / conv_wavek_multi_kernel<MT, NT, WAVES, DEPTH, TAG, SPREAD>: a shape (its key: launch_wavek) for the tags 1 ... 3 and 0 = any other layer.
+// The product build carries the three forms the planner uses -- 4 waves, 2 slabs in flight, the spread schedules -- ; the forms that measured slower (8 waves, 3 slabs
+// in flight, the burst schedules: CHANGELOG.md rounds 2-4) exist in the experiments build.
+#define AAE_WAVEK_ROWS(X, K, key, MT, NT, WAVES, DEPTH, SPREAD) \
+    X(form == key && tag == 1, (aae::K<MT, NT, WAVES, DEPTH, 1, SPREAD>), (aae::conv_wavek_smem<MT, NT, WAVES>())) \
+    X(form == key && tag == 2, (aae::K<MT, NT, WAVES, DEPTH, 2, SPREAD>), (aae::conv_wavek_smem<MT, NT, WAVES>())) \
+    X(form == key && tag == 3, (aae::K<MT, NT, WAVES, DEPTH, 3, SPREAD>), (aae::conv_wavek_smem<MT, NT, WAVES>())) \
+    X(form == key && (tag < 1 || tag > 3), (aae::K<MT, NT, WAVES, DEPTH, 0, SPREAD>), (aae::conv_wavek_smem<MT, NT, WAVES>()))
+constexpr int kWaveKOtherSchedule = 100000;      // added to a shape's key: the load schedule that is not the shape's default (burst for 64 x 64 and 32 x 32 tiles, spread for 64 x 32)
+#ifdef AAE_EXPERIMENTS
+#define AAE_WAVEK_FORMS_EXPERIMENTS(X) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, kWaveKOtherSchedule + 242, 2, 2, 4, 2, false) AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, kWaveKOtherSchedule + 1142, 1, 1, 4, 2, false) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 243, 2, 2, 4, 3, false) AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 282, 2, 2, 8, 2, false) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 143, 2, 1, 4, 3, false) AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 1143, 1, 1, 4, 3, false) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 182, 2, 1, 8, 2, false) AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 1182, 1, 1, 8, 2, false)
+// (grouped: the spread schedule for 64 x 32 tiles and three slabs in flight for them -- aae_multi_impl.h, launch_wavek_multi)
+#define AAE_WAVEK_MULTI_FORMS_EXPERIMENTS(X) \
+    AAE_WAVEK_ROWS(X, conv_wavek_multi_kernel, kWaveKOtherSchedule + 142, 2, 1, 4, 2, true) AAE_WAVEK_ROWS(X, conv_wavek_multi_kernel, 143, 2, 1, 4, 3, false)
+#else
+#define AAE_WAVEK_FORMS_EXPERIMENTS(X)
+#define AAE_WAVEK_MULTI_FORMS_EXPERIMENTS(X)
+#endif
+#define AAE_WAVEK_FORMS(X) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 242, 2, 2, 4, 2, true) AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 142, 2, 1, 4, 2, false) \
+    AAE_WAVEK_ROWS(X, conv_wavek_f32_kernel, 1142, 1, 1, 4, 2, true) AAE_WAVEK_FORMS_EXPERIMENTS(X)
+#define AAE_WAVEK_MULTI_FORMS(X) \
+    AAE_WAVEK_ROWS(X, conv_wavek_multi_kernel, 242, 2, 2, 4, 2, true) AAE_WAVEK_ROWS(X, conv_wavek_multi_kernel, 142, 2, 1, 4, 2, false) \
+    AAE_WAVEK_ROWS(X, conv_wavek_multi_kernel, 1142, 1, 1, 4, 2, true) AAE_WAVEK_MULTI_FORMS_EXPERIMENTS(X)
+
+// conv_first_f32_kernel<KS, C, IN_U8, OUT_PLANES, VEC4, GROUP_SPLIT> at the layer's own LDS size (first_lds: Layer::first_smem) and the grouped query's
+// conv_first_multi_kernel<KS, C, IN_U8, VEC4, GROUP_SPLIT> at the CU's 160 KB
+#define AAE_FIRST_ROWS(X, C) \
+    X(cin == C && group_split && vec4, (aae::conv_first_f32_kernel<5, C, true, false, true, true>), first_lds) \
+    X(cin == C && group_split && u8, (aae::conv_first_f32_kernel<5, C, true, false, false, true>), first_lds) \
+    X(cin == C && group_split, (aae::conv_first_f32_kernel<5, C, false, false, false, true>), first_lds) \
+    X(cin == C && planes && vec4, (aae::conv_first_f32_kernel<5, C, true, true, true>), first_lds) \
+    X(cin == C && planes && u8, (aae::conv_first_f32_kernel<5, C, true, true>), first_lds) \
+    X(cin == C && planes, (aae::conv_first_f32_kernel<5, C, false, true>), first_lds) \
+    X(cin == C && vec4, (aae::conv_first_f32_kernel<5, C, true, false, true>), first_lds) \
+    X(cin == C && u8, (aae::conv_first_f32_kernel<5, C, true, false>), first_lds) \
+    X(cin == C, (aae::conv_first_f32_kernel<5, C, false, false>), first_lds)
+#define AAE_FIRST_FORMS(X) AAE_FIRST_ROWS(X, 3) AAE_FIRST_ROWS(X, 1)
+#define AAE_FIRST_MULTI_ROWS(X, C, GROUP_SPLIT) \
+    X(cin == C && group_split == GROUP_SPLIT && vec4, (aae::conv_first_multi_kernel<5, C, true, true, GROUP_SPLIT>), 160 * 1024) \
+    X(cin == C && group_split == GROUP_SPLIT && u8, (aae::conv_first_multi_kernel<5, C, true, false, GROUP_SPLIT>), 160 * 1024) \
+    X(cin == C && group_split == GROUP_SPLIT, (aae::conv_first_multi_kernel<5, C, false, false, GROUP_SPLIT>), 160 * 1024)
+#define AAE_FIRST_MULTI_FORMS(X) AAE_FIRST_MULTI_ROWS(X, 3, true) AAE_FIRST_MULTI_ROWS(X, 3, false) AAE_FIRST_MULTI_ROWS(X, 1, true) AAE_FIRST_MULTI_ROWS(X, 1, false)
+
+// dense_gemv_f32_kernel<MQ, TICKET> and dense_gemv_multi_kernel<MQ>: the activation chunk + half sums of MQ batch rows, or the finishing block's row-group sums
+constexpr int gemv_smem(int mq, bool ticket) {
+    return (ticket && 2 * mq * aae::kGemvChunk * (int)sizeof(float) + 16 < aae::kGemvTicketSmem) ? aae::kGemvTicketSmem : 2 * mq * aae::kGemvChunk * (int)sizeof(float) + 16;
+}
+#define AAE_GEMV_ROWS(X, TICKET) \
+    X(ticket == TICKET && mq == 1, (aae::dense_gemv_f32_kernel<1, TICKET>), gemv_smem(1, TICKET)) X(ticket == TICKET && mq == 2, (aae::dense_gemv_f32_kernel<2, TICKET>), gemv_smem(2, TICKET)) \
+    X(ticket == TICKET && mq == 3, (aae::dense_gemv_f32_kernel<3, TICKET>), gemv_smem(3, TICKET)) X(ticket == TICKET && mq == 4, (aae::dense_gemv_f32_kernel<4, TICKET>), gemv_smem(4, TICKET)) \
+    X(ticket == TICKET && mq == 8, (aae::dense_gemv_f32_kernel<8, TICKET>), gemv_smem(8, TICKET))
+#ifdef AAE_EXPERIMENTS
+#define AAE_GEMV_FORMS(X) AAE_GEMV_ROWS(X, true) AAE_GEMV_ROWS(X, false)       // (without the in-launch finish: a reduce launch adds up the chunk rows)
+#else
+#define AAE_GEMV_FORMS(X) AAE_GEMV_ROWS(X, true)
+#endif
+#define AAE_GEMV_MULTI_FORMS(X) \
+    X(mq == 1, (aae::dense_gemv_multi_kernel<1>), gemv_smem(1, true)) X(mq == 2, (aae::dense_gemv_multi_kernel<2>), gemv_smem(2, true)) \
+    X(mq == 3, (aae::dense_gemv_multi_kernel<3>), gemv_smem(3, true)) X(mq == 4, (aae::dense_gemv_multi_kernel<4>), gemv_smem(4, true))
+
+// the grouped query's scans, as far as aae_multi_impl.h launches them: scan_stream_multi_kernel<NQ> and scan_resident_multi_kernel<RH>
+#define AAE_SCAN_STREAM_MULTI_ROWS(X, NQ) X(nq == NQ, (aae::scan_stream_multi_kernel<NQ>), NQ * 128 * (int)sizeof(float) + aae::kScanTicketSmem)
+#define AAE_SCAN_STREAM_MULTI_FORMS(X) AAE_SCAN_STREAM_MULTI_ROWS(X, 1) AAE_SCAN_STREAM_MULTI_ROWS(X, 2) AAE_SCAN_STREAM_MULTI_ROWS(X, 3) AAE_SCAN_STREAM_MULTI_ROWS(X, 4)
+#define AAE_SCAN_RESIDENT_MULTI_ROWS(X, RH) X(rh == RH, (aae::scan_resident_multi_kernel<RH>), (aae::scan_resident_smem<false, RH>()))
+#define AAE_SCAN_RESIDENT_MULTI_FORMS(X) AAE_SCAN_RESIDENT_MULTI_ROWS(X, 1) AAE_SCAN_RESIDENT_MULTI_ROWS(X, 2) AAE_SCAN_RESIDENT_MULTI_ROWS(X, 4)
+
+#ifdef AAE_EXPERIMENTS
+// detect_chain_kernel<MQ, S0, S1, S2>: (batch class, wave-tile shape code of conv2 ... conv4) -- what plan_wavek gives the reference network at B = 1, 2, 3, 4
+#define AAE_CHAIN_FORMS(X) \
+    X(mq == 1 && shapes == 0, (aae::detect_chain_kernel<1, 0, 0, 0>), aae::kChainSmem) X(mq == 2 && shapes == 100, (aae::detect_chain_kernel<2, 1, 0, 0>), aae::kChainSmem) \
+    X(mq == 4 && shapes == 10, (aae::detect_chain_kernel<4, 0, 1, 0>), aae::kChainSmem) X(mq == 4 && shapes == 210, (aae::detect_chain_kernel<4, 2, 1, 0>), aae::kChainSmem)
+// conv_wino_phase_kernel<TH, TW, SWAP, GEOM>: the four polyphase components as launches of their own, per block geometry
+#define AAE_WINO_PHASE_ROWS(X, GEOM) \
+    X(geom == GEOM && eh && ew, (aae::conv_wino_phase_kernel<3, 3, false, GEOM>), (aae::wino_smem_bytes<GEOM>())) \
+    X(geom == GEOM && eh && !ew, (aae::conv_wino_phase_kernel<3, 2, false, GEOM>), (aae::wino_smem_bytes<GEOM>())) \
+    X(geom == GEOM && !eh && ew, (aae::conv_wino_phase_kernel<3, 2, true, GEOM>), (aae::wino_smem_bytes<GEOM>())) \
+    X(geom == GEOM && !eh && !ew, (aae::conv_wino_phase_kernel<2, 2, false, GEOM>), (aae::wino_smem_bytes<GEOM>()))
+#define AAE_WINO_PHASE_FORMS(X) AAE_WINO_PHASE_ROWS(X, 0) AAE_WINO_PHASE_ROWS(X, 2)
+#endif
+
+// The LDS ceiling of every form of every list, raised when a handle is created (on the device the handle lives on: the attribute belongs to the device's copy of
+// the function) -- never in front of a launch.  A grouped query cannot run without an encoder handle, so the handle's creation covers its kernels too.
+static void set_launch_attributes(const aae_encoder* enc) {
+    wino_set_attributes();
+    AAE_IGEMM_FORMS(AAE_FORM_CEILING)
+    AAE_X3H_FORMS(AAE_FORM_CEILING)
+    AAE_WAVEK_FORMS(AAE_FORM_CEILING)
+    AAE_WAVEK_MULTI_FORMS(AAE_FORM_CEILING)
+    AAE_GEMV_FORMS(AAE_FORM_CEILING)
+    AAE_GEMV_MULTI_FORMS(AAE_FORM_CEILING)
+    AAE_SCAN_STREAM_MULTI_FORMS(AAE_FORM_CEILING)
+    AAE_SCAN_RESIDENT_MULTI_FORMS(AAE_FORM_CEILING)
+    AAE_FIRST_MULTI_FORMS(AAE_FORM_CEILING)
+#ifdef AAE_EXPERIMENTS
+    AAE_CHAIN_FORMS(AAE_FORM_CEILING)
+    AAE_WINO_PHASE_FORMS(AAE_FORM_CEILING)
+#endif
+    if (!enc->layers.empty() && enc->layers[0].kind == KIND_FIRST_MFMA) {          // (a decoder's context has no conv1)
+        const int first_lds = enc->layers[0].first_smem;
+        AAE_FIRST_FORMS(AAE_FORM_CEILING)
+    }
+}
+
+// ------------------------------------------------------------ shared pieces of the conv launches
+// What the four conv argument records (ConvIgemmArgs of the encoder and of the decoder, ConvWaveKArgs, ConvIgemmX3hArgs) take from the layer: bias / folded batch
+// norm, the geometry of M output rows, the byte sizes of the two buffer views -- and the one check that the input fits a 32-bit view (fp32 and fp16-pair
+// activations: 4 bytes per element either way).
+template <class Args>
+static int conv_layer_args(Args& a, const Layer& L, int M, const char* name) {
+    a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift;
     a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.Cout; a.CoutPad = L.CoutPad;
-    a.KS = L.KS; a.S = L.S; a.pt = L.pt; a.pl = L.pl; a.M = M; a.relu = L.relu; a.stagger = enc->igemm_stagger;
+    a.KS = L.KS; a.S = L.S; a.pt = L.pt; a.pl = L.pl; a.M = M; a.relu = L.relu;
     const unsigned long long x_bytes = (unsigned long long)(M / (L.Ho * L.Wo)) * L.H * L.W * L.Cin * sizeof(float);
-    if (x_bytes >= 0xFFFFFFF0ull)
-        return fail(AAE_ERR_UNSUPPORTED, "%s: input activation of %llu bytes exceeds the 4 GiB buffer view; use a smaller batch", name, x_bytes);
     a.x_bytes = (unsigned)x_bytes;
     a.slabs_total = (int)(L.K() / 32);
     a.wp_bytes = (unsigned)((unsigned long long)a.slabs_total * 8ull * L.CoutPad * 16ull);
+    if (x_bytes >= 0xFFFFFFF0ull)
+        return fail(AAE_ERR_UNSUPPORTED, "%s: input activation of %llu bytes exceeds the 4 GiB buffer view; use a smaller batch", name, x_bytes);
+    return AAE_OK;
+}
+
+// the second launch of a split-K layer: partial sums [splits][M][Cout] -> bias / ReLU / batch norm -> the layer's output (planes: fp16 pairs of value * out_scale)
+static int launch_reduce_tail(const aae_encoder* enc, const Layer& L, const float* partial, float* out, long long M, int splits, bool planes, float out_scale,
+                              hipStream_t stream, Timer& tm, const char* name) {
+    aae::SplitKReduceArgs r;
+    r.partial = partial; r.bias = L.bias; r.bn_scale = L.bn_scale; r.bn_shift = L.bn_shift; r.out = out;
+    r.MN = M * L.Cout; r.Cout = L.Cout; r.splits = splits; r.relu = L.relu;
+    r.out_planes = planes ? 1 : 0; r.out_scale = out_scale; r.sat_flag = planes ? t_x3h_flag : nullptr;
+    launch_splitk_reduce(r, stream, enc->reduce_small != 0);
+    return launch_done(tm, 0.0, "%s:splitk_reduce", name);
+}
+
+static bool launch_igemm_form(int form, bool dma, int tag, dim3 grid, int smem, hipStream_t stream, const aae::ConvIgemmArgs& a) {
+    const dim3 block(256);
+    AAE_IGEMM_FORMS(AAE_FORM_LAUNCH_SMEM)
+    return false;
+}
+
+static int launch_igemm(aae_encoder* enc, const Layer& L, const float* x, int M, float* out, float* partial,
+                        hipStream_t stream, Timer& tm, const char* name, int tag = 0) {
+    aae::ConvIgemmArgs a;
+    a.x = x; a.wp = L.wp; a.stagger = enc->igemm_stagger;
+    if (int rc = conv_layer_args(a, L, M, name)) return rc;
     a.num_mt = ceil_div(M, 128);
     a.num_nt = L.CoutPad / 128;
     choose_splits(enc, a.num_mt * a.num_nt, a.slabs_total, &a.splits, &a.slabs_per_split);
@@ -43,99 +252,54 @@ static int launch_igemm(aae_encoder* enc, const Layer& L, const float* x, int M,
     const bool dma = true;                     // (the register-staged operand path: experiments build)
 #endif
     const char* kname = dma ? "conv_igemm_f32_dma" : "conv_igemm_f32";
-    char label[96];
+    const char* missing = "%s: no igemm instantiation for form %d, tag %d in this build";
     if (a.splits == 1) {
         a.out = out;
-        // A buffers only (32 KB: three blocks per CU); grids too small to give every CU three blocks keep the
-        // 64 KB footprint so that the blocks spread two per CU instead of 3/2/1
-        const int kBregSmem = nblk >= enc->igemm_breg_min_blocks ? 2 * aae::kSlabFloatsA * 4 : aae::kConvIgemmSmem;
 #ifdef AAE_EXPERIMENTS
         const bool breg = dma && enc->igemm_breg && tag >= 1 && tag <= 3;
 #else
         const bool breg = tag >= 1 && tag <= 3;   // (weights through LDS for the conv layers: experiments build)
 #endif
-        if (breg) kname = "conv_igemm_f32_dma_breg";
         // 128 x 256 block tiles (each wave 64 x 128) where the layer is wide enough and the grid stays large
         if (breg && enc->igemm_breg_wide && (tag == 1 || tag == 2) && L.CoutPad % 256 == 0 &&
             a.num_mt * (L.CoutPad / 256) >= enc->igemm_breg_wide_min_blocks) {
             a.num_nt = L.CoutPad / 256;
-            const int wide_blocks = a.num_mt * a.num_nt;
-            constexpr int smem = 2 * aae::kSlabFloatsA * 4;
-            if (tag == 1) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 1, true, 4>), dim3(wide_blocks), dim3(256), smem, stream, a);
-            else AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 2, true, 4>), dim3(wide_blocks), dim3(256), smem, stream, a);
-            snprintf(label, sizeof(label), "%s:conv_igemm_f32_dma_breg_n256 M=%d N=%d K=%lld", name, M, L.Cout, L.K());
-            note_kernel({label, flops});
-            AAE_HIP_TRY(hipGetLastError());
-            return tm.mark();
+            if (!launch_igemm_form(IGEMM_BREG_N256, dma, tag, dim3(a.num_mt * a.num_nt), 2 * aae::kSlabFloatsA * 4, stream, a))
+                return fail(AAE_ERR_RUNTIME, missing, name, IGEMM_BREG_N256, tag);
+            return launch_done(tm, flops, "%s:conv_igemm_f32_dma_breg_n256 M=%d N=%d K=%lld", name, M, L.Cout, L.K());
         }
-        if (breg && tag == 1) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 1, true>), dim3(nblk), dim3(256), kBregSmem, stream, a);
-        else if (breg && tag == 2) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 2, true>), dim3(nblk), dim3(256), kBregSmem, stream, a);
-        else if (breg && tag == 3) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 3, true>), dim3(nblk), dim3(256), kBregSmem, stream, a);
-#ifdef AAE_EXPERIMENTS
-        else if (dma && tag == 1) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 1>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        else if (dma && tag == 2) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 2>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        else if (dma && tag == 3) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true, false, 3>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        else if (!dma) AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, false>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-#endif
-        else AAE_LAUNCH((aae::conv_igemm_f32_kernel<false, true>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        snprintf(label, sizeof(label), "%s:%s M=%d N=%d K=%lld", name, kname, M, L.Cout, L.K());
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
+        // weights in registers: A buffers only (32 KB: three blocks per CU); grids too small to give every CU three blocks keep the
+        // 64 KB footprint so that the blocks spread two per CU instead of 3/2/1
+        const int smem = breg && nblk >= enc->igemm_breg_min_blocks ? 2 * aae::kSlabFloatsA * 4 : aae::kConvIgemmSmem;
+        if (!launch_igemm_form(breg ? IGEMM_BREG : IGEMM_PLAIN, dma, tag, dim3(nblk), smem, stream, a))
+            return fail(AAE_ERR_RUNTIME, missing, name, breg ? IGEMM_BREG : IGEMM_PLAIN, tag);
+        return launch_done(tm, flops, "%s:%s M=%d N=%d K=%lld", name, breg ? "conv_igemm_f32_dma_breg" : kname, M, L.Cout, L.K());
     }
     a.out = partial;
-#ifdef AAE_EXPERIMENTS
-    if (!dma) AAE_LAUNCH((aae::conv_igemm_f32_kernel<true, false>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-    else
-#endif
-    AAE_LAUNCH((aae::conv_igemm_f32_kernel<true, true>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-    snprintf(label, sizeof(label), "%s:%s_splitk%d M=%d N=%d K=%lld", name, kname, a.splits, M, L.Cout, L.K());
-    note_kernel({label, flops});
-    AAE_HIP_TRY(hipGetLastError());
-    if (int rc = tm.mark()) return rc;
-    aae::SplitKReduceArgs r;
-    r.partial = partial; r.bias = L.bias; r.bn_scale = L.bn_scale; r.bn_shift = L.bn_shift; r.out = out;
-    r.MN = (long long)M * L.Cout; r.Cout = L.Cout; r.splits = a.splits; r.relu = L.relu;
-    r.out_planes = 0; r.out_scale = 1.f;
-    launch_splitk_reduce(r, stream, enc->reduce_small != 0);
-    snprintf(label, sizeof(label), "%s:splitk_reduce", name);
-    note_kernel({label, 0.0});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    if (!launch_igemm_form(IGEMM_SPLITK, dma, tag, dim3(nblk), aae::kConvIgemmSmem, stream, a)) return fail(AAE_ERR_RUNTIME, missing, name, IGEMM_SPLITK, tag);
+    if (int rc = launch_done(tm, flops, "%s:%s_splitk%d M=%d N=%d K=%lld", name, kname, a.splits, M, L.Cout, L.K())) return rc;
+    return launch_reduce_tail(enc, L, partial, out, M, a.splits, false, 1.f, stream, tm, name);
 }
 
-// wave-split-K igemm (conv_wavek_f32.h): small M -- the per-detection batches
-template <int MT, int NT, int WAVES, int DEPTH, bool SPREAD = false>
-static void launch_wavek_t(const aae::ConvWaveKArgs& a, int tag, int nblk, hipStream_t stream) {
-    constexpr int smem = aae::conv_wavek_smem<MT, NT, WAVES>();
-    // TAG only makes the symbol unique per encoder layer (separate rows in rocprofv3 --stats)
-    if (tag == 1) {
-        (void)hipFuncSetAttribute((const void*)aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 1, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 1, SPREAD>), dim3(nblk), dim3(64 * WAVES), smem, stream, a);
-    } else if (tag == 2) {
-        (void)hipFuncSetAttribute((const void*)aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 2, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 2, SPREAD>), dim3(nblk), dim3(64 * WAVES), smem, stream, a);
-    } else if (tag == 3) {
-        (void)hipFuncSetAttribute((const void*)aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 3, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 3, SPREAD>), dim3(nblk), dim3(64 * WAVES), smem, stream, a);
-    } else {
-        (void)hipFuncSetAttribute((const void*)aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 0, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        AAE_LAUNCH((aae::conv_wavek_f32_kernel<MT, NT, WAVES, DEPTH, 0, SPREAD>), dim3(nblk), dim3(64 * WAVES), smem, stream, a);
-    }
+// wave-split-K igemm (conv_wavek_f32.h): small M -- the per-detection batches.  form: the plan's shape key (+ kWaveKOtherSchedule)
+static bool launch_wavek_form(int form, int tag, int waves, dim3 grid, hipStream_t stream, const aae::ConvWaveKArgs& a) {
+    const dim3 block(64 * waves);
+    AAE_WAVEK_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
 
+// (conv_layer_args' 4 GiB check is not expected to fire here -- plan_wavek refuses such a layer (plan_wavek_core), and the grouped query plans rows that plan_wavek
+//  accepted for the same detections (multi_encoder_groupable) or at most three 16 x 16 images (plan_mid_ragged) -- ; its answer is ignored, so this function returns
+//  what it returned before the check moved into the shared fill)
 static aae::ConvWaveKArgs wavek_args(const aae_encoder* enc, const Layer& L, const WaveKPlan& w, const float* x, int M, float* out, float* partial,
                                      unsigned long long* tickets, unsigned nonce, int tag) {
     aae::ConvWaveKArgs a;
-    a.x = x; a.wp = L.wp; a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift; a.out = out;
+    a.x = x; a.wp = L.wp; a.out = out;
     a.partial = partial; a.partial_bytes = (unsigned)w.partial_bytes; a.tickets = tickets; a.nonce = nonce;
-    a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.Cout; a.CoutPad = L.CoutPad;
-    a.KS = L.KS; a.S = L.S; a.pt = L.pt; a.pl = L.pl; a.M = M; a.relu = L.relu; a.ablate = enc->wavek_ablate; a.pingpong = enc->wavek_pingpong; a.spread = enc->wavek_spread;
+    (void)conv_layer_args(a, L, M, "wave-split-K layer");
+    a.ablate = enc->wavek_ablate; a.pingpong = enc->wavek_pingpong; a.spread = enc->wavek_spread;
     a.timeline = (enc->wavek_timeline && tag >= 1 && tag <= 3 && w.blocks() <= 512)       // (the debug buffer holds 512 blocks per layer)
                      ? enc->wavek_timeline + (size_t)(tag - 1) * 512 * 8 : nullptr;
-    a.x_bytes = (unsigned)((unsigned long long)(M / (L.Ho * L.Wo)) * L.H * L.W * L.Cin * sizeof(float));
-    a.slabs_total = (int)(L.K() / 32);
-    a.wp_bytes = (unsigned)((unsigned long long)a.slabs_total * 8ull * L.CoutPad * 16ull);
     a.num_mt = w.num_mt; a.num_nt = w.num_nt; a.gsplits = w.gsplits;
     a.tail_tiles = w.tail_tiles; a.tail_gsplits = w.tail_g;
     return a;
@@ -144,51 +308,31 @@ static aae::ConvWaveKArgs wavek_args(const aae_encoder* enc, const Layer& L, con
 static int launch_wavek(aae_encoder* enc, const Layer& L, const WaveKPlan& w, const float* x, int M, float* out, float* partial,
                         unsigned long long* tickets, unsigned nonce, hipStream_t stream, Timer& tm, const char* name, int tag) {
     const aae::ConvWaveKArgs a = wavek_args(enc, L, w, x, M, out, partial, tickets, nonce, tag);
-    const int nblk = w.blocks();
-    const int key = (w.MT == 1 ? 1000 : 0) + w.NT * 100 + w.waves * 10 + w.depth;
-    // The product build carries the three forms the planner uses -- 4 waves, 2 slabs in flight, the spread schedules -- ; the forms
-    // that measured slower (8 waves, 3 slabs in flight, the burst schedules: CHANGELOG.md rounds 2-4) exist in the experiments build.
-    switch (key + ((key == 242 && !(a.spread & 1)) || (key == 1142 && !(a.spread & 2)) ? 100000 : 0)) {
-        case 242: launch_wavek_t<2, 2, 4, 2, true>(a, tag, nblk, stream); break;
-        case 142: launch_wavek_t<2, 1, 4, 2>(a, tag, nblk, stream); break;
-        case 1142: launch_wavek_t<1, 1, 4, 2, true>(a, tag, nblk, stream); break;
-#ifdef AAE_EXPERIMENTS
-        case 100242: launch_wavek_t<2, 2, 4, 2>(a, tag, nblk, stream); break;
-        case 101142: launch_wavek_t<1, 1, 4, 2>(a, tag, nblk, stream); break;
-        case 243: launch_wavek_t<2, 2, 4, 3>(a, tag, nblk, stream); break;
-        case 282: launch_wavek_t<2, 2, 8, 2>(a, tag, nblk, stream); break;
-        case 143: launch_wavek_t<2, 1, 4, 3>(a, tag, nblk, stream); break;
-        case 1143: launch_wavek_t<1, 1, 4, 3>(a, tag, nblk, stream); break;
-        case 182: launch_wavek_t<2, 1, 8, 2>(a, tag, nblk, stream); break;
-        case 1182: launch_wavek_t<1, 1, 8, 2>(a, tag, nblk, stream); break;
-#endif
-        default: return fail(AAE_ERR_RUNTIME, "%s: no wave-split-K instantiation for MT=%d NT=%d waves=%d depth=%d spread=%d in this build", name, w.MT, w.NT, w.waves, w.depth, a.spread);
-    }
-    char label[128], tail[24] = "";
+    const int key = wavek_shape_key(w);
+    const bool burst = (key == 242 && !(a.spread & 1)) || (key == 1142 && !(a.spread & 2));
+    if (!launch_wavek_form(key + (burst ? kWaveKOtherSchedule : 0), tag, w.waves, dim3(w.blocks()), stream, a))
+        return fail(AAE_ERR_RUNTIME, "%s: no wave-split-K instantiation for MT=%d NT=%d waves=%d depth=%d spread=%d in this build", name, w.MT, w.NT, w.waves, w.depth, a.spread);
+    char tail[24] = "";
     if (w.tail_tiles > 0) snprintf(tail, sizeof(tail), "t%dx%d", w.tail_tiles, w.tail_g);       // (e.g. g1t64x4: the last 64 tiles cut four ways)
-    snprintf(label, sizeof(label), "%s:conv_wavek_f32_%dx%d_w%d_d%d_g%d%s M=%d N=%d K=%lld", name, 32 * w.MT, 32 * w.NT, w.waves, w.depth,
-             w.gsplits, tail, M, L.Cout, L.K());
-    note_kernel({label, 2.0 * (double)M * (double)L.K() * (double)L.Cout});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    return launch_done(tm, 2.0 * (double)M * (double)L.K() * (double)L.Cout, "%s:conv_wavek_f32_%dx%d_w%d_d%d_g%d%s M=%d N=%d K=%lld", name, 32 * w.MT, 32 * w.NT,
+                       w.waves, w.depth, w.gsplits, tail, M, L.Cout, L.K());
+}
+
+static bool launch_x3h_form(int form, bool dma, int tag, dim3 grid, hipStream_t stream, const aae::ConvIgemmX3hArgs& a) {
+    const dim3 block(form == X3H_WIDE256 || form == X3H_WIDE128 ? 512 : 256);          // (the wide tiles: 8 waves)
+    AAE_X3H_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
 
 // f32x3h variant: x and (unless out_f32) out are fp16 (hi, lo) pairs of value * 2^x3h_act_shift (x3h_pair_index layout).
 static int launch_igemm_x3h(aae_encoder* enc, const Layer& L, const void* x, int M, void* out, bool out_f32, float* partial,
                             hipStream_t stream, Timer& tm, const char* name, int tag = 0) {
     aae::ConvIgemmX3hArgs a;
-    a.x = static_cast<const unsigned short*>(x); a.wp = L.wp16; a.bias = L.bias; a.bn_scale = L.bn_scale; a.bn_shift = L.bn_shift;
-    a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.Cout; a.CoutPad = L.CoutPad;
-    a.KS = L.KS; a.S = L.S; a.pt = L.pt; a.pl = L.pl; a.M = M; a.relu = L.relu;
-    const unsigned long long in_bytes = (unsigned long long)(M / (L.Ho * L.Wo)) * L.H * L.W * L.Cin * 4;
-    if (in_bytes >= 0xFFFFFFF0ull)
-        return fail(AAE_ERR_UNSUPPORTED, "%s: input activation of %llu bytes exceeds the 4 GiB buffer view; use a smaller batch", name, in_bytes);
-    a.x_bytes = (unsigned)in_bytes;
+    a.x = static_cast<const unsigned short*>(x); a.wp = L.wp16;
+    if (int rc = conv_layer_args(a, L, M, name)) return rc;
     a.inv_scale = ldexpf(1.f, -(enc->x3h_act_shift + L.w_shift));
     a.out_scale = ldexpf(1.f, enc->x3h_act_shift);
     a.sat_flag = out_f32 ? nullptr : t_x3h_flag;
-    a.slabs_total = (int)(L.K() / 32);
-    a.wp_bytes = (unsigned)((unsigned long long)a.slabs_total * 8ull * L.CoutPad * 16ull);
     a.num_mt = ceil_div(M, 128);
     a.num_nt = L.CoutPad / 128;
     choose_splits(enc, a.num_mt * a.num_nt, a.slabs_total, &a.splits, &a.slabs_per_split);
@@ -200,114 +344,42 @@ static int launch_igemm_x3h(aae_encoder* enc, const Layer& L, const void* x, int
     const bool dma = true;
 #endif
     const char* kname = dma ? "conv_igemm_x3h_dma" : "conv_igemm_x3h";
-    char label[96];
+    const char* missing = "%s: no f32x3h igemm instantiation for form %d, tag %d in this build";
     // 256 x 256 tiles, 8 waves of 64 x 128 (LDS traffic per MFMA -33 %): layers with Cout % 256 == 0 whose grid still fills the chip
-    if (dma && !out_f32 && enc->x3h_wide256 && L.CoutPad % 256 == 0 && tag >= 1 && tag <= 3 &&
-        ceil_div(M, 256) * (L.CoutPad / 256) >= enc->x3h_wide256_min_blocks) {
-        a.num_mt = ceil_div(M, 256);
-        a.num_nt = L.CoutPad / 256;
-        a.splits = 1;
-        a.slabs_per_split = a.slabs_total;
-        a.out = out;
-        const int wide_blocks = a.num_mt * a.num_nt;
-        constexpr int smem = aae::kX3hWideSmem;
-        if (tag == 1) {
-            (void)hipFuncSetAttribute((const void*)aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            AAE_LAUNCH((aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 1>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        } else if (tag == 2) {
-            (void)hipFuncSetAttribute((const void*)aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            AAE_LAUNCH((aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 2>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        } else {
-            (void)hipFuncSetAttribute((const void*)aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            AAE_LAUNCH((aae::conv_igemm_x3h_wide_kernel<aae::X3H_OUT_PLANES, 3>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        }
-        snprintf(label, sizeof(label), "%s:conv_igemm_x3h_wide256 M=%d N=%d K=%lld", name, M, L.Cout, L.K());
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
-    }
+    const bool wide256 = dma && !out_f32 && enc->x3h_wide256 && L.CoutPad % 256 == 0 && tag >= 1 && tag <= 3 &&
+                         ceil_div(M, 256) * (L.CoutPad / 256) >= enc->x3h_wide256_min_blocks;
+    bool wide128 = false;
 #ifdef AAE_EXPERIMENTS
     // 256 x 128 tiles (8 waves, one block per CU) when they still give every CU a block
-    if (dma && !out_f32 && tag >= 1 && tag <= 3 && enc->x3h_wide_min_blocks > 0 &&
-        ceil_div(M, 256) * a.num_nt >= enc->x3h_wide_min_blocks) {
+    wide128 = !wide256 && dma && !out_f32 && tag >= 1 && tag <= 3 && enc->x3h_wide_min_blocks > 0 && ceil_div(M, 256) * a.num_nt >= enc->x3h_wide_min_blocks;
+#endif
+    if (wide256 || wide128) {
         a.num_mt = ceil_div(M, 256);
+        if (wide256) a.num_nt = L.CoutPad / 256;
         a.splits = 1;
         a.slabs_per_split = a.slabs_total;
         a.out = out;
-        const int wide_blocks = a.num_mt * a.num_nt;
-        constexpr int smem = aae::x3h_dma_smem<4>();
-        if (tag == 1) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 1, 4>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        else if (tag == 2) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 2, 4>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        else AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 3, 4>), dim3(wide_blocks), dim3(512), smem, stream, a);
-        snprintf(label, sizeof(label), "%s:conv_igemm_x3h_dma256 M=%d N=%d K=%lld", name, M, L.Cout, L.K());
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
+        const int form = wide256 ? X3H_WIDE256 : X3H_WIDE128;
+        if (!launch_x3h_form(form, dma, tag, dim3(a.num_mt * a.num_nt), stream, a)) return fail(AAE_ERR_RUNTIME, missing, name, form, tag);
+        return launch_done(tm, flops, "%s:conv_igemm_x3h_%s M=%d N=%d K=%lld", name, wide256 ? "wide256" : "dma256", M, L.Cout, L.K());
     }
-#endif
     if (a.splits == 1) {
         a.out = out;
-        if (dma) {
-            if (out_f32) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_F32>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-            else if (tag == 1) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 1>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-            else if (tag == 2) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 2>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-            else if (tag == 3) AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES, 3>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-            else AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PLANES>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        }
-#ifdef AAE_EXPERIMENTS
-        else {
-            if (out_f32) AAE_LAUNCH((aae::conv_igemm_x3h_kernel<aae::X3H_OUT_F32>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-            else AAE_LAUNCH((aae::conv_igemm_x3h_kernel<aae::X3H_OUT_PLANES>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-        }
-#endif
-        snprintf(label, sizeof(label), "%s:%s M=%d N=%d K=%lld", name, kname, M, L.Cout, L.K());
-        note_kernel({label, flops});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
+        const int form = out_f32 ? X3H_F32 : X3H_PLANES;
+        if (!launch_x3h_form(form, dma, tag, dim3(nblk), stream, a)) return fail(AAE_ERR_RUNTIME, missing, name, form, tag);
+        return launch_done(tm, flops, "%s:%s M=%d N=%d K=%lld", name, kname, M, L.Cout, L.K());
     }
     a.out = partial;
-#ifdef AAE_EXPERIMENTS
-    if (!dma) AAE_LAUNCH((aae::conv_igemm_x3h_kernel<aae::X3H_OUT_PARTIAL>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-    else
-#endif
-    AAE_LAUNCH((aae::conv_igemm_x3h_dma_kernel<aae::X3H_OUT_PARTIAL>), dim3(nblk), dim3(256), aae::kConvIgemmSmem, stream, a);
-    snprintf(label, sizeof(label), "%s:%s_splitk%d M=%d N=%d K=%lld", name, kname, a.splits, M, L.Cout, L.K());
-    note_kernel({label, flops});
-    AAE_HIP_TRY(hipGetLastError());
-    if (int rc = tm.mark()) return rc;
-    aae::SplitKReduceArgs r;
-    r.partial = partial; r.bias = L.bias; r.bn_scale = L.bn_scale; r.bn_shift = L.bn_shift; r.out = static_cast<float*>(out);
-    r.MN = (long long)M * L.Cout; r.Cout = L.Cout; r.splits = a.splits; r.relu = L.relu;
-    r.out_planes = out_f32 ? 0 : 1; r.out_scale = a.out_scale; r.sat_flag = out_f32 ? nullptr : t_x3h_flag;
-    launch_splitk_reduce(r, stream, enc->reduce_small != 0);
-    snprintf(label, sizeof(label), "%s:splitk_reduce", name);
-    note_kernel({label, 0.0});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    if (!launch_x3h_form(X3H_PARTIAL, dma, tag, dim3(nblk), stream, a)) return fail(AAE_ERR_RUNTIME, missing, name, X3H_PARTIAL, tag);
+    if (int rc = launch_done(tm, flops, "%s:%s_splitk%d M=%d N=%d K=%lld", name, kname, a.splits, M, L.Cout, L.K())) return rc;
+    return launch_reduce_tail(enc, L, partial, static_cast<float*>(out), M, a.splits, !out_f32, a.out_scale, stream, tm, name);
 }
 
-template <int KS, int C>
-static void launch_first_t(const aae::ConvFirstArgs& a, bool u8, bool planes, dim3 grid, int smem, hipStream_t stream, bool group_split = false) {
-    const bool vec4 = u8 && a.vec4;
-    if (group_split && !planes) {                 // per-detection batches: one block per 32-pixel group (grid.z = 4)
-        const dim3 g4(grid.x, grid.y, 4);
-        (void)hipFuncSetAttribute((const void*)aae::conv_first_f32_kernel<KS, C, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        (void)hipFuncSetAttribute((const void*)aae::conv_first_f32_kernel<KS, C, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        (void)hipFuncSetAttribute((const void*)aae::conv_first_f32_kernel<KS, C, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (vec4) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, false, true, true>), g4, dim3(256), smem, stream, a);
-        else if (u8) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, false, false, true>), g4, dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, false, false, false, true>), g4, dim3(256), smem, stream, a);
-        return;
-    }
-    if (planes) {
-        if (vec4) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, true, true>), grid, dim3(256), smem, stream, a);
-        else if (u8) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, true>), grid, dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, false, true>), grid, dim3(256), smem, stream, a);
-    } else {
-        if (vec4) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, false, true>), grid, dim3(256), smem, stream, a);
-        else if (u8) AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, true, false>), grid, dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::conv_first_f32_kernel<KS, C, false, false>), grid, dim3(256), smem, stream, a);
-    }
+// group_split (never with planes): per-detection batches, one block per 32-pixel group -- the caller's grid has z = 4
+static bool launch_first_form(int cin, bool u8, bool vec4, bool planes, bool group_split, dim3 grid, int smem, hipStream_t stream, const aae::ConvFirstArgs& a) {
+    const dim3 block(256);
+    AAE_FIRST_FORMS(AAE_FORM_LAUNCH_SMEM)
+    return false;
 }
 
 // arguments of the first-layer kernel for a batch of B crops; returns the number of tile runs (blocks along grid.x)
@@ -335,16 +407,13 @@ static int launch_first(aae_encoder* enc, const Layer& L, const void* x, bool u8
     if (prep) a.prep = *prep;
     else a.prep.n = 0;
     const int runs = first_core_args(enc, L, x, u8, B, out, planes, a);
-    const dim3 grid(runs + (a.prep.n > 0 ? 1 : 0), ceil_div(L.Cout, 128));    // + the ticket-preparation block
     // per-detection batches: the four 32-pixel groups of every tile go to four blocks (10.6 -> ? us at B = 1)
     const bool group_split = !planes && a.total_tiles <= enc->first_group_split_max_tiles;
-    if (L.Cin == 3) launch_first_t<5, 3>(a, u8, planes, grid, L.first_smem, stream, group_split);
-    else launch_first_t<5, 1>(a, u8, planes, grid, L.first_smem, stream, group_split);
-    char label[96];
-    snprintf(label, sizeof(label), "conv1:conv_first_f32%s M=%d N=%d K=%lld", group_split ? "_g4" : "", B * L.Ho * L.Wo, L.Cout, L.K());
-    note_kernel({label, 2.0 * (double)B * L.Ho * L.Wo * (double)L.K() * L.Cout});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    const dim3 grid(runs + (a.prep.n > 0 ? 1 : 0), ceil_div(L.Cout, 128), group_split ? 4 : 1);    // + the ticket-preparation block
+    if (!launch_first_form(L.Cin, u8, u8 && a.vec4, planes, group_split, grid, L.first_smem, stream, a))
+        return fail(AAE_ERR_RUNTIME, "conv1: no first-layer instantiation for %d input channels in this build", L.Cin);
+    return launch_done(tm, 2.0 * (double)B * L.Ho * L.Wo * (double)L.K() * L.Cout, "conv1:conv_first_f32%s M=%d N=%d K=%lld", group_split ? "_g4" : "",
+                       B * L.Ho * L.Wo, L.Cout, L.K());
 }
 
 static int launch_generic(aae_encoder* enc, const Layer& L, const void* x, bool u8, long long B, float* out,
@@ -358,11 +427,7 @@ static int launch_generic(aae_encoder* enc, const Layer& L, const void* x, bool 
     if (blocks > 8192) blocks = 8192;
     if (u8) AAE_LAUNCH((aae::conv_direct_generic_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else AAE_LAUNCH((aae::conv_direct_generic_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    char label[96];
-    snprintf(label, sizeof(label), "%s:conv_direct_generic", name);
-    note_kernel({label, 2.0 * (double)B * L.Ho * L.Wo * (double)L.K() * L.Cout});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    return launch_done(tm, 2.0 * (double)B * L.Ho * L.Wo * (double)L.K() * L.Cout, "%s:conv_direct_generic", name);
 }
 
 // dense layer at B <= 8: weight-streaming GEMV + the fixed-order chunk reduction
@@ -382,51 +447,28 @@ static aae::DenseGemvArgs gemv_args(const Layer& D, const float* x, int B, float
     return a;
 }
 
+static bool launch_gemv_form(int mq, bool ticket, dim3 grid, hipStream_t stream, const aae::DenseGemvArgs& a) {
+    const dim3 block(256);
+    AAE_GEMV_FORMS(AAE_FORM_LAUNCH)
+    return false;
+}
+
 static int launch_dense_gemv(aae_encoder* enc, const Layer& D, const float* x, int B, float* out, float* partial,
                              unsigned long long* tickets, unsigned nonce, hipStream_t stream, Timer& tm) {
     aae::DenseGemvArgs a = gemv_args(D, x, B, partial);
     const int chunks = ceil_div(a.K, aae::kGemvChunk);
     const dim3 grid(chunks, D.CoutPad / 128);
     const int MQ = B <= 4 ? B : 8;
-    int smem = 2 * MQ * aae::kGemvChunk * (int)sizeof(float) + 16;
     const bool ticket = tickets && gemv_uses_ticket(enc, D);
-    char label[96];
     if (ticket) {
         a.bias = D.bias; a.bn_scale = D.bn_scale; a.bn_shift = D.bn_shift; a.out = out;
         a.tickets = tickets;
         a.nonce = nonce; a.relu = D.relu;
-        if (smem < aae::kGemvTicketSmem) smem = aae::kGemvTicketSmem;
-        if (MQ == 1) AAE_LAUNCH((aae::dense_gemv_f32_kernel<1, true>), grid, dim3(256), smem, stream, a);
-        else if (MQ == 2) AAE_LAUNCH((aae::dense_gemv_f32_kernel<2, true>), grid, dim3(256), smem, stream, a);
-        else if (MQ == 3) AAE_LAUNCH((aae::dense_gemv_f32_kernel<3, true>), grid, dim3(256), smem, stream, a);
-        else if (MQ == 4) AAE_LAUNCH((aae::dense_gemv_f32_kernel<4, true>), grid, dim3(256), smem, stream, a);
-        else AAE_LAUNCH((aae::dense_gemv_f32_kernel<8, true>), grid, dim3(256), smem, stream, a);
-        snprintf(label, sizeof(label), "dense:dense_gemv_f32_ticket chunks=%d M=%d N=%d K=%d", chunks, B, D.Cout, a.K);
-        note_kernel({label, 2.0 * B * (double)D.K() * D.Cout});
-        AAE_HIP_TRY(hipGetLastError());
-        return tm.mark();
     }
-#ifndef AAE_EXPERIMENTS
-    return fail(AAE_ERR_RUNTIME, "dense GEMV without its in-launch finish: experiments build only");      // (forward_impl never plans it here)
-#else
-    a.bias = nullptr; a.bn_scale = nullptr; a.bn_shift = nullptr; a.out = nullptr; a.tickets = nullptr; a.nonce = 0; a.relu = 0;
-    if (MQ == 1) AAE_LAUNCH((aae::dense_gemv_f32_kernel<1>), grid, dim3(256), smem, stream, a);
-    else if (MQ == 2) AAE_LAUNCH((aae::dense_gemv_f32_kernel<2>), grid, dim3(256), smem, stream, a);
-    else if (MQ == 3) AAE_LAUNCH((aae::dense_gemv_f32_kernel<3>), grid, dim3(256), smem, stream, a);
-    else if (MQ == 4) AAE_LAUNCH((aae::dense_gemv_f32_kernel<4>), grid, dim3(256), smem, stream, a);
-    else AAE_LAUNCH((aae::dense_gemv_f32_kernel<8>), grid, dim3(256), smem, stream, a);
-    snprintf(label, sizeof(label), "dense:dense_gemv_f32 chunks=%d M=%d N=%d K=%d", chunks, B, D.Cout, a.K);
-    note_kernel({label, 2.0 * B * (double)D.K() * D.Cout});
-    AAE_HIP_TRY(hipGetLastError());
-    if (int rc = tm.mark()) return rc;
-    aae::SplitKReduceArgs r;
-    r.partial = partial; r.bias = D.bias; r.bn_scale = D.bn_scale; r.bn_shift = D.bn_shift; r.out = out;
-    r.MN = (long long)B * D.Cout; r.Cout = D.Cout; r.splits = chunks; r.relu = D.relu; r.out_planes = 0; r.out_scale = 1.f;
-    launch_splitk_reduce(r, stream, enc->reduce_small != 0);
-    note_kernel({"dense:splitk_reduce", 0.0});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
-#endif
+    // (without the in-launch finish: the experiments build -- forward_impl never plans it in the product build)
+    if (!launch_gemv_form(MQ, ticket, grid, stream, a)) return fail(AAE_ERR_RUNTIME, "dense GEMV for %d rows%s: no instantiation in this build", MQ, ticket ? "" : " without its in-launch finish");
+    if (int rc = launch_done(tm, 2.0 * B * (double)D.K() * D.Cout, "dense:dense_gemv_f32%s chunks=%d M=%d N=%d K=%d", ticket ? "_ticket" : "", chunks, B, D.Cout, a.K)) return rc;
+    return ticket ? AAE_OK : launch_reduce_tail(enc, D, partial, out, B, chunks, false, 1.f, stream, tm, "dense");
 }
 
 // One extra ticket range the first kernel of the forward prepares for a launch that FOLLOWS the encoder on the same
@@ -468,10 +510,12 @@ static bool chain_eligible(const aae_encoder* enc, int B, const std::vector<Wave
     return false;
 }
 
-template <int MQ, int S0, int S1, int S2>
-static void launch_chain_t(const aae::DetectChainArgs& a, int grid, hipStream_t stream) {
-    (void)hipFuncSetAttribute((const void*)aae::detect_chain_kernel<MQ, S0, S1, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, aae::kChainSmem);
-    AAE_LAUNCH_RESIDENT((aae::detect_chain_kernel<MQ, S0, S1, S2>), dim3(grid), dim3(256), aae::kChainSmem, stream, a);
+// (every block resident at once: the kernel waits grid-wide)
+#define AAE_FORM_LAUNCH_RESIDENT(when, kernel, lds) if (when) { AAE_LAUNCH_RESIDENT(kernel, grid, block, lds, stream, a); return true; }
+static bool launch_chain_form(int mq, int shapes, dim3 grid, hipStream_t stream, const aae::DetectChainArgs& a) {
+    const dim3 block(256);
+    AAE_CHAIN_FORMS(AAE_FORM_LAUNCH_RESIDENT)
+    return false;
 }
 
 static int launch_detect_chain(aae_encoder* enc, int B, const std::vector<WaveKPlan>& plans, const std::vector<unsigned>& nonces, unsigned gemv_nonce,
@@ -513,20 +557,11 @@ static int launch_detect_chain(aae_encoder* enc, int B, const std::vector<WaveKP
     int grid = enc->detect_chain_blocks;
     if (enc->cu_count > 0 && grid > enc->cu_count) grid = enc->cu_count;
     if (grid < 1) grid = 1;
-    const int key = (B <= 2 ? B : 4) * 1000 + chain_shape_code(plans[1]) * 100 + chain_shape_code(plans[2]) * 10 + chain_shape_code(plans[3]);
-    switch (key) {                                              // (kChainVariants)
-        case 1000: launch_chain_t<1, 0, 0, 0>(a, grid, stream); break;
-        case 2100: launch_chain_t<2, 1, 0, 0>(a, grid, stream); break;
-        case 4010: launch_chain_t<4, 0, 1, 0>(a, grid, stream); break;
-        case 4210: launch_chain_t<4, 2, 1, 0>(a, grid, stream); break;
-        default: return fail(AAE_ERR_RUNTIME, "no persistent per-detection kernel for batch %d / wave-tile shapes %d", B, key % 1000);
-    }
-    char label[128];
-    snprintf(label, sizeof(label), "chain:detect_chain_f32 B=%d blocks=%d shapes=%d%d%d phases=conv2..conv%zu+dense%s", B, grid, chain_shape_code(plans[1]),
-             chain_shape_code(plans[2]), chain_shape_code(plans[3]), nl, a.has_scan ? "+scan" : "");
-    note_kernel({label, flops});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    const int shapes = chain_shape_code(plans[1]) * 100 + chain_shape_code(plans[2]) * 10 + chain_shape_code(plans[3]);
+    if (!launch_chain_form(B <= 2 ? B : 4, shapes, dim3(grid), stream, a))               // (kChainVariants)
+        return fail(AAE_ERR_RUNTIME, "no persistent per-detection kernel for batch %d / wave-tile shapes %d", B, shapes);
+    return launch_done(tm, flops, "chain:detect_chain_f32 B=%d blocks=%d shapes=%d%d%d phases=conv2..conv%zu+dense%s", B, grid, chain_shape_code(plans[1]),
+                       chain_shape_code(plans[2]), chain_shape_code(plans[3]), nl, a.has_scan ? "+scan" : "");
 }
 
 #endif  // AAE_EXPERIMENTS
@@ -534,13 +569,10 @@ static int launch_detect_chain(aae_encoder* enc, int B, const std::vector<WaveKP
 #ifdef AAE_EXPERIMENTS
 // A conv layer as four polyphase Winograd launches (conv_winograd_f32.h): the phases add up in the output buffer, the last one applies
 // bias / ReLU / BN.  The 3 x 3-tap phase goes first (it stores), the 2 x 2-tap one last.
-template <int GEOM>
-static void launch_wino_phase(const aae::ConvWinoArgs& a, int eh, int ew, unsigned grid, hipStream_t stream) {
-    constexpr int smem = aae::wino_smem_bytes<GEOM>();
-    if (eh && ew) AAE_LAUNCH((aae::conv_wino_phase_kernel<3, 3, false, GEOM>), dim3(grid), dim3(512), smem, stream, a);
-    else if (eh) AAE_LAUNCH((aae::conv_wino_phase_kernel<3, 2, false, GEOM>), dim3(grid), dim3(512), smem, stream, a);
-    else if (ew) AAE_LAUNCH((aae::conv_wino_phase_kernel<3, 2, true, GEOM>), dim3(grid), dim3(512), smem, stream, a);
-    else AAE_LAUNCH((aae::conv_wino_phase_kernel<2, 2, false, GEOM>), dim3(grid), dim3(512), smem, stream, a);
+static bool launch_wino_phase_form(int geom, int eh, int ew, dim3 grid, hipStream_t stream, const aae::ConvWinoArgs& a) {
+    const dim3 block(512);
+    AAE_WINO_PHASE_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
 #endif
 
@@ -565,7 +597,6 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
     a.xcd_cols = wino_xcd_cols(enc, L);
     const unsigned grid = aae::wino_grid_blocks(a.regions, L.Cout / 64, a.xcd_cols);
     const double tiles = (double)B * (L.Ho / 2) * (L.Wo / 2);
-    char label[128];
 #ifdef AAE_EXPERIMENTS
     if (enc->winograd == 2) {
         // one launch per phase, the phases add up in the output buffer (A/B of the one-launch form: 2 % slower)
@@ -574,14 +605,11 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
             const int eh = order[i][0], ew = order[i][1];
             a.eh = eh; a.ew = ew; a.U = L.wino[2 * eh + ew];
             a.mode = i == 0 ? 0 : (i == 3 ? 2 : 1);
-            if (L.wino_geom == 0) launch_wino_phase<0>(a, eh, ew, grid, stream);
-            else launch_wino_phase<2>(a, eh, ew, grid, stream);      // (four windows of their own: WinoGeom<2>)
+            if (!launch_wino_phase_form(L.wino_geom == 0 ? 0 : 2, eh, ew, dim3(grid), stream, a))      // (geometry 1 as four windows of their own: WinoGeom<2>)
+                return fail(AAE_ERR_RUNTIME, "%s: no Winograd phase instantiation for geometry %d", name, L.wino_geom);
             const int taps = (eh ? 3 : 2) * (ew ? 3 : 2), points = ((eh ? 3 : 2) + 1) * ((ew ? 3 : 2) + 1);
-            snprintf(label, sizeof(label), "%s:conv_wino_f32 phase %d%d (%d taps as %d products per 2x2 outputs) M=%d N=%d C=%d", name, eh, ew, taps, points,
-                     B * L.Ho * L.Wo, L.Cout, L.Cin);
-            note_kernel({label, 2.0 * tiles * points * (double)L.Cin * (double)L.Cout});
-            AAE_HIP_TRY(hipGetLastError());
-            if (int rc = tm.mark()) return rc;
+            if (int rc = launch_done(tm, 2.0 * tiles * points * (double)L.Cin * (double)L.Cout, "%s:conv_wino_f32 phase %d%d (%d taps as %d products per 2x2 outputs) M=%d N=%d C=%d",
+                                     name, eh, ew, taps, points, B * L.Ho * L.Wo, L.Cout, L.Cin)) return rc;
         }
         return AAE_OK;
     }
@@ -593,10 +621,8 @@ static int launch_winograd(aae_encoder* enc, const Layer& L, const float* x, int
     wino_layer_launch(L.wino_geom, enc->winograd_wide, enc->winograd_stage32, grid, stream, p, enc->winograd_static_halo);
     // (the record carries the flops the kernel EXECUTES -- 49 products per 2 x 2 outputs and channel pair where the direct form
     //  multiplies 100 -- so that its TFLOP/s figure is a statement about the kernel)
-    snprintf(label, sizeof(label), "%s:conv_wino_f32 layer (25 taps as 49 products per 2x2 outputs) M=%d N=%d C=%d", name, B * L.Ho * L.Wo, L.Cout, L.Cin);
-    note_kernel({label, 2.0 * tiles * 49.0 * (double)L.Cin * (double)L.Cout});
-    AAE_HIP_TRY(hipGetLastError());
-    return tm.mark();
+    return launch_done(tm, 2.0 * tiles * 49.0 * (double)L.Cin * (double)L.Cout, "%s:conv_wino_f32 layer (25 taps as 49 products per 2x2 outputs) M=%d N=%d C=%d", name,
+                       B * L.Ho * L.Wo, L.Cout, L.Cin);
 }
 
 // The round-fill rule on a block count: do `blocks` Winograd blocks fill winograd_min_fill_pct per cent of the rounds they occupy (winograd_rule has the

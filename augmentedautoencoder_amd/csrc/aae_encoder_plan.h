@@ -210,6 +210,8 @@ struct WaveKPlan {
     size_t partial_bytes = 0;
     int blocks() const { return (num_mt * num_nt - tail_tiles) * gsplits + tail_tiles * tail_g; }
 };
+// the shape a plan asks of the kernel: the key of the wave-split-K form lists (aae_encoder_launch.h)
+static int wavek_shape_key(const WaveKPlan& w) { return (w.MT == 1 ? 1000 : 0) + w.NT * 100 + w.waves * 10 + w.depth; }
 
 // Does a forward of batch B run in f32x3h?  precision 1: always.  precision 2 ("where it is faster"): only when the first
 // implicit-GEMM layer has at least x3h_min_tiles 64 x 64 output tiles -- below that the layers do not fill the chip, the

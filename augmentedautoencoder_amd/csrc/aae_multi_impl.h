@@ -52,7 +52,6 @@ struct MultiPlan {
 
 static thread_local int t_multi_launches = 0;      // kernel launches queued by the calling thread's last multi call (its grouped part)
 
-static int wavek_shape_key(const WaveKPlan& w) { return (w.MT == 1 ? 1000 : 0) + w.NT * 100 + w.waves * 10 + w.depth; }
 // Is the plan's wave tile one of the instantiated grouped forms (launch_wavek_multi: the defaults -- 4 waves, 2 slabs in flight, the spread schedules)?
 static bool wavek_multi_instantiated(const aae_encoder* enc, const WaveKPlan& w) {
     const int key = wavek_shape_key(w);
@@ -409,51 +408,34 @@ static int plan_multi(const aae_multi_item* items, int n_items, bool scan_only, 
     return AAE_OK;
 }
 
-template <int KS, int C>
-static void launch_first_multi_t(const aae::ConvFirstMultiArgs& m, bool u8, bool vec4, dim3 grid, int smem, hipStream_t stream) {
-    // (the dynamic-LDS ceiling of every instantiation is raised ONCE per process, to the CU's 160 KB: not a runtime call per grouped frame)
-    static const bool once = ((void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-    (void)once;
-    if (u8 && vec4) AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, true, true>), grid, dim3(256), smem, stream, m);
-    else if (u8) AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, true, false>), grid, dim3(256), smem, stream, m);
-    else AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, false, false>), grid, dim3(256), smem, stream, m);
+// The dispatch of the grouped kernels, from the form lists of aae_encoder_launch.h (the LDS ceiling of every row was raised when the objects' encoder handles were
+// created: set_launch_attributes).  false: no such form in this build.
+// conv1 across objects -- group_split: per-detection groups, grid.z = 4 and one ticket-preparation block per object; otherwise the whole-tile form of the mid-batch groups
+static bool launch_first_multi_form(int cin, bool u8, bool vec4, bool group_split, dim3 grid, int smem, hipStream_t stream, const aae::ConvFirstMultiArgs& a) {
+    const dim3 block(256);
+    vec4 = u8 && vec4;
+    AAE_FIRST_MULTI_FORMS(AAE_FORM_LAUNCH_SMEM)
+    return false;
 }
-
-// whole-tile form of the grouped conv1 (mid-batch groups): no ticket preparation blocks, grid.z = 1
-template <int KS, int C>
-static void launch_first_multi_tiles_t(const aae::ConvFirstMultiArgs& m, bool u8, bool vec4, dim3 grid, int smem, hipStream_t stream) {
-    static const bool once = ((void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_first_multi_kernel<KS, C, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-    (void)once;
-    if (u8 && vec4) AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, true, true, false>), grid, dim3(256), smem, stream, m);
-    else if (u8) AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, true, false, false>), grid, dim3(256), smem, stream, m);
-    else AAE_LAUNCH((aae::conv_first_multi_kernel<KS, C, false, false, false>), grid, dim3(256), smem, stream, m);
+static bool launch_wavek_multi_form(int form, int tag, dim3 grid, hipStream_t stream, const aae::ConvWaveKMultiArgs& a) {
+    const dim3 block(256);
+    AAE_WAVEK_MULTI_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
-
-template <int MT, int NT, bool SPREAD, int DEPTH = 2>
-static void launch_wavek_multi_t(const aae::ConvWaveKMultiArgs& m, int tag, int nblk, hipStream_t stream) {
-    constexpr int smem = aae::conv_wavek_smem<MT, NT, 4>();
-    // TAG only makes the symbol unique per encoder layer (separate rows in rocprofv3 --stats)
-    static const bool once = ((void)hipFuncSetAttribute((const void*)aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 0, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 1, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 2, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem),
-                              (void)hipFuncSetAttribute((const void*)aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 3, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem), true);
-    (void)once;
-    if (tag == 1) AAE_LAUNCH((aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 1, SPREAD>), dim3(nblk), dim3(256), smem, stream, m);
-    else if (tag == 2) AAE_LAUNCH((aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 2, SPREAD>), dim3(nblk), dim3(256), smem, stream, m);
-    else if (tag == 3) AAE_LAUNCH((aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 3, SPREAD>), dim3(nblk), dim3(256), smem, stream, m);
-    else AAE_LAUNCH((aae::conv_wavek_multi_kernel<MT, NT, 4, DEPTH, 0, SPREAD>), dim3(nblk), dim3(256), smem, stream, m);
+static bool launch_gemv_multi_form(int mq, dim3 grid, hipStream_t stream, const aae::DenseGemvMultiArgs& a) {
+    const dim3 block(256);
+    AAE_GEMV_MULTI_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
-
-template <int RH>
-static void launch_scan_resident_multi_t(const aae::ScanResidentMultiArgs& m, int nblk, hipStream_t stream) {
-    constexpr int smem = aae::scan_resident_smem<false, RH>();
-    static const bool once = ((void)hipFuncSetAttribute((const void*)aae::scan_resident_multi_kernel<RH>, hipFuncAttributeMaxDynamicSharedMemorySize, smem), true);
-    (void)once;
-    AAE_LAUNCH((aae::scan_resident_multi_kernel<RH>), dim3(nblk), dim3(aae::kScanResidentThreads), smem, stream, m);
+static bool launch_scan_stream_multi_form(int nq, dim3 grid, hipStream_t stream, const aae::ScanMultiArgs& a) {
+    const dim3 block(256);
+    AAE_SCAN_STREAM_MULTI_FORMS(AAE_FORM_LAUNCH)
+    return false;
+}
+static bool launch_scan_resident_multi_form(int rh, dim3 grid, hipStream_t stream, const aae::ScanResidentMultiArgs& a) {
+    const dim3 block(aae::kScanResidentThreads);
+    AAE_SCAN_RESIDENT_MULTI_FORMS(AAE_FORM_LAUNCH)
+    return false;
 }
 
 // The codebook scans of a mid-batch group: objects whose query takes the query-resident arg-max form on an fp32 codebook (the block normalises its own queries) share ONE
@@ -497,9 +479,7 @@ static int launch_mid_scans(const aae_multi_item* items, const MultiPlan& mp, co
         if (!nk) continue;
         m.range.n = nk;
         m.range.first[nk] = at;
-        if (rh == 1) launch_scan_resident_multi_t<1>(m, at, stream);
-        else if (rh == 2) launch_scan_resident_multi_t<2>(m, at, stream);
-        else launch_scan_resident_multi_t<4>(m, at, stream);
+        if (!launch_scan_resident_multi_form(rh, dim3(at), stream, m)) return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped resident scan for %d row parts in this build", rh);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
     }
@@ -552,11 +532,7 @@ static int launch_scan_multi(const MultiPlan& mp, const std::vector<int>& member
         at += p.sp.nblk;
     }
     m.range.first[members.size()] = at;
-    const int smem = n * 128 * (int)sizeof(float) + aae::kScanTicketSmem;
-    if (n == 1) AAE_LAUNCH((aae::scan_stream_multi_kernel<1>), dim3(at), dim3(256), smem, stream, m);
-    else if (n == 2) AAE_LAUNCH((aae::scan_stream_multi_kernel<2>), dim3(at), dim3(256), smem, stream, m);
-    else if (n == 3) AAE_LAUNCH((aae::scan_stream_multi_kernel<3>), dim3(at), dim3(256), smem, stream, m);
-    else AAE_LAUNCH((aae::scan_stream_multi_kernel<4>), dim3(at), dim3(256), smem, stream, m);
+    if (!launch_scan_stream_multi_form(n, dim3(at), stream, m)) return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped stream scan for %d detections per object in this build", n);
     AAE_HIP_TRY(hipGetLastError());
     ++t_multi_launches;
     return AAE_OK;
@@ -575,21 +551,17 @@ static void wavek_multi_append(aae::ConvWaveKMultiArgs& m, int& at, const aae::C
 // ... and its launch: false where no grouped instantiation exists for the shape key (wavek_multi_instantiated).  `variants`: the encoder whose A/B options
 // reach the experiments build's extra forms (the per-detection conv layers; nullptr elsewhere)
 static bool launch_wavek_multi(int key, const aae::ConvWaveKMultiArgs& m, int tag, int nblk, hipStream_t stream, const aae_encoder* variants) {
+    int form = key;
 #ifdef AAE_EXPERIMENTS
     // (A/B: the spread load schedule for 64 x 32 tiles -- loads between the MFMAs of its two accumulators: 8 x 1 434 against 400 us,
     //  16 x 1 807 against 743: slower, as on single objects in round 4; profiles/r13_multi/depth_and_schedule_ab.jsonl)
-    if (variants && key == 142 && (variants->multi_force_depth & 0x10000)) { launch_wavek_multi_t<2, 1, true>(m, tag, nblk, stream); return true; }
+    if (variants && key == 142 && (variants->multi_force_depth & 0x10000)) form = kWaveKOtherSchedule + 142;
     // three slabs in flight for the 64 x 32 layers (option multi_force_depth): conv4 of a few-detection frame streams 26 MB of cold weights
     // per object against 5 us of MFMA work -- more bytes in flight changed NOTHING (8 x 1: 397 vs 397 us, profiles/r13_multi/depth_ab.jsonl)
-    if (variants && key == 143) { launch_wavek_multi_t<2, 1, false, 3>(m, tag, nblk, stream); return true; }
+    if (!variants && key == 143) return false;
 #endif
     (void)variants;
-    switch (key) {
-        case 1142: launch_wavek_multi_t<1, 1, true>(m, tag, nblk, stream); return true;
-        case 142: launch_wavek_multi_t<2, 1, false>(m, tag, nblk, stream); return true;
-        case 242: launch_wavek_multi_t<2, 2, true>(m, tag, nblk, stream); return true;
-    }
-    return false;
+    return launch_wavek_multi_form(form, tag, dim3(nblk), stream, m);
 }
 
 // The Winograd problem table of conv layer li across `members` (a per-detection group or a mid-batch group): geometry, per-object pointers, the prefix sum over the
@@ -669,8 +641,8 @@ static int launch_encoder_multi(const aae_multi_item* items, const MultiPlan& mp
         m.range.first[members.size()] = at;
         const Layer& L0 = enc0->layers[0];
         const dim3 grid(at + (unsigned)members.size(), ceil_div(L0.Cout, 128), 4);
-        if (L0.Cin == 3) launch_first_multi_t<5, 3>(m, u8, vec4 != 0, grid, L0.first_smem, stream);
-        else launch_first_multi_t<5, 1>(m, u8, vec4 != 0, grid, L0.first_smem, stream);
+        if (!launch_first_multi_form(L0.Cin, u8, vec4 != 0, true, grid, L0.first_smem, stream, m))
+            return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped first-layer instantiation for %d input channels in this build", L0.Cin);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
     }
@@ -730,12 +702,7 @@ static int launch_encoder_multi(const aae_multi_item* items, const MultiPlan& mp
         m.range.first[members.size()] = at;
         const Layer& D0 = enc0->dense;
         const dim3 grid(at, D0.CoutPad / 128);
-        int smem = 2 * nmax * aae::kGemvChunk * (int)sizeof(float) + 16;
-        if (smem < aae::kGemvTicketSmem) smem = aae::kGemvTicketSmem;
-        if (nmax == 1) AAE_LAUNCH((aae::dense_gemv_multi_kernel<1>), grid, dim3(256), smem, stream, m);
-        else if (nmax == 2) AAE_LAUNCH((aae::dense_gemv_multi_kernel<2>), grid, dim3(256), smem, stream, m);
-        else if (nmax == 3) AAE_LAUNCH((aae::dense_gemv_multi_kernel<3>), grid, dim3(256), smem, stream, m);
-        else AAE_LAUNCH((aae::dense_gemv_multi_kernel<4>), grid, dim3(256), smem, stream, m);
+        if (!launch_gemv_multi_form(nmax, grid, stream, m)) return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped dense GEMV for %d detections per object in this build", nmax);
         AAE_HIP_TRY(hipGetLastError());
         ++t_multi_launches;
     }
@@ -777,8 +744,8 @@ static int launch_mid_group(const aae_multi_item* items, const MultiPlan& mp, co
             m.range.first[members.size()] = at;
             const Layer& L0 = enc0->layers[0];
             const dim3 grid((unsigned)at, ceil_div(L0.Cout, 128), 1);
-            if (L0.Cin == 3) launch_first_multi_tiles_t<5, 3>(m, u8, vec4 != 0, grid, L0.first_smem, stream);
-            else launch_first_multi_tiles_t<5, 1>(m, u8, vec4 != 0, grid, L0.first_smem, stream);
+            if (!launch_first_multi_form(L0.Cin, u8, vec4 != 0, false, grid, L0.first_smem, stream, m))
+                return fail(AAE_ERR_RUNTIME, "multi-object query: no grouped first-layer instantiation for %d input channels in this build", L0.Cin);
             AAE_HIP_TRY(hipGetLastError());
             ++t_multi_launches;
         }
