@@ -19,6 +19,7 @@ AAE_SCAN_AUTO, AAE_SCAN_GEMV, AAE_SCAN_MFMA, AAE_SCAN_STREAM, AAE_SCAN_STREAM_2L
 AAE_SCAN_AUTO_PACKED, AAE_SCAN_AUTO_RH2, AAE_SCAN_AUTO_FIN, AAE_SCAN_AUTO_TOPK_ROWS = 7, 8, 9, 10
 AAE_ABI_VERSION = 3
 AAE_MODEL_RECONST, AAE_MODEL_CAD = 0, 1
+AAE_SCENE_MAX_DRAWS = 256
 AAE_ICP_MAX_PROBLEMS, AAE_ICP_MAX_POINTS = 16, 4096
 AAE_ICP_DEPTH_ONLY, AAE_ICP_NO_DEPTH, AAE_ICP_NO_DEPTH_ZERO_T = 1, 2, 4
 
@@ -48,6 +49,8 @@ EXPORTED_SYMBOLS = (
     'aae_decoder_forward_timed', 'aae_decoder_kernel_label', 'aae_decoder_kernel_flops', 'aae_decoder_activation_info',
     'aae_mesh_create', 'aae_mesh_destroy', 'aae_render_workspace_bytes', 'aae_render_embedding_views', 'aae_render_embedding_views_timed',
     'aae_render_frames',
+    'aae_mesh_set_create', 'aae_mesh_set_destroy', 'aae_render_scenes_workspace_bytes', 'aae_render_scenes', 'aae_render_scenes_timed',
+    'aae_overlay_blend',
     'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
 )
 
@@ -224,6 +227,20 @@ def declare_render(lib):
     lib.aae_render_frames.restype = c_int
     lib.aae_render_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_int, POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]
+    lib.aae_mesh_set_create.restype = c_int
+    lib.aae_mesh_set_create.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p)]
+    lib.aae_mesh_set_destroy.restype = None
+    lib.aae_mesh_set_destroy.argtypes = [c_void_p]
+    lib.aae_render_scenes_workspace_bytes.restype = c_size_t
+    lib.aae_render_scenes_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
+    scenes = [c_void_p, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_int, c_int, POINTER(RenderParams), c_void_p, c_void_p, c_void_p,
+              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.aae_render_scenes.restype = c_int
+    lib.aae_render_scenes.argtypes = scenes
+    lib.aae_render_scenes_timed.restype = c_int
+    lib.aae_render_scenes_timed.argtypes = scenes + [POINTER(c_float)]
+    lib.aae_overlay_blend.restype = c_int
+    lib.aae_overlay_blend.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]
     return lib
 
 

@@ -11,6 +11,7 @@
 
 #include "../../include/aae_hip.h"
 #include "kernels/render_raster.h"
+#include "kernels/render_scene.h"
 
 namespace aae_host {
 void set_last_error(const char* msg);          // aae_host_types.h: the thread's aae_last_error() text lives in aae_hip.hip
@@ -22,6 +23,11 @@ struct aae_mesh {
     float* colors = nullptr;
     int32_t* faces = nullptr;
     int V = 0, F = 0, model = 0;
+};
+
+struct aae_mesh_set {
+    aae_render::SceneMesh* table = nullptr;        // device, [n]: written once by aae_mesh_set_create
+    int n = 0, Vmax = 0, Fmax = 0, model = 0;
 };
 
 namespace aae_render {
@@ -137,6 +143,113 @@ static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int
     return AAE_OK;
 }
 
+struct SceneLayout {
+    size_t rect, bounds, draw_obj, vtx, vary, keys, total;
+};
+
+static inline int scene_raster_blocks(int Fmax) { return (Fmax + RENDER_BLOCK - 1) / RENDER_BLOCK; }
+
+static SceneLayout scene_layout(int Vmax, int Fmax, int n_draws, int n_scenes, int W, int H) {
+    SceneLayout l;
+    size_t o = 0;
+    l.rect = o;     o += up256((size_t)n_scenes * 4 * sizeof(int32_t));
+    l.bounds = o;   o += up256((size_t)n_draws * scene_raster_blocks(Fmax) * 4 * sizeof(int32_t));
+    l.draw_obj = o; o += up256((size_t)n_draws * sizeof(int32_t));
+    l.vtx = o;      o += up256((size_t)n_draws * Vmax * sizeof(RcVertex));
+    l.vary = o;     o += up256((size_t)n_draws * Vmax * RC_VARY * sizeof(float));
+    l.keys = o;     o += up256((size_t)n_scenes * W * H * sizeof(unsigned long long));
+    l.total = o;
+    return l;
+}
+
+#define AAE_SCENE_MAX_SCENES 65535           /* the scene is blockIdx.y, and a uint16 in the draw table */
+#define AAE_SCENE_MAX_MESHES 65536           /* the mesh is a uint16 in the draw table */
+
+// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+static int scene_run(const aae_mesh_set* set, const int32_t* obj_ids, const int32_t* scene_ids, const double* Rs, const double* ts, int n_draws,
+                     int n_scenes, const aae_render_params* p, void* bgr_out, float* depth_out, int32_t* draw_out, int32_t* tri_out, int32_t* bbs_out,
+                     int32_t* visible_out, void* ws, size_t ws_bytes, void* stream_, float* kernel_ms, const char* who) {
+    if (!set || !obj_ids || !scene_ids || !Rs || !ts || !p || !bgr_out || !depth_out || !bbs_out || !visible_out || !ws)
+        return rfail(AAE_ERR_INVALID, "%s: null argument", who);
+    if (n_draws < 1 || n_draws > AAE_SCENE_MAX_DRAWS)
+        return rfail(AAE_ERR_UNSUPPORTED, "%s: %d draws outside [1,%d] per call (split by scene)", who, n_draws, AAE_SCENE_MAX_DRAWS);
+    if (n_scenes < 1 || n_scenes > AAE_SCENE_MAX_SCENES)
+        return rfail(AAE_ERR_UNSUPPORTED, "%s: %d scenes outside [1,%d] per call", who, n_scenes, AAE_SCENE_MAX_SCENES);
+    if (!rc_scene_fits((uint64_t)n_draws, (uint64_t)set->Fmax))
+        return rfail(AAE_ERR_UNSUPPORTED, "%s: %d draws of up to %d faces do not fit the 32-bit index of the visibility key", who, n_draws, set->Fmax);
+    if (p->W < 1 || p->H < 1 || p->W > AAE_RENDER_MAX_DIM || p->H > AAE_RENDER_MAX_DIM)
+        return rfail(AAE_ERR_UNSUPPORTED, "%s: render dims %dx%d outside [1,%d]", who, p->W, p->H, AAE_RENDER_MAX_DIM);
+    if (p->K[3] != 0.0 || p->K[6] != 0.0 || p->K[7] != 0.0)
+        return rfail(AAE_ERR_INVALID, "%s: K[1,0], K[2,0] and K[2,1] must be 0", who);
+    if (!(p->clip_near > 0.0) || !(p->clip_far > p->clip_near)) return rfail(AAE_ERR_INVALID, "%s: need 0 < near < far", who);
+    SceneArgs a;
+    memset(&a.draws, 0, sizeof(a.draws));
+    for (int d = 0; d < n_draws; ++d) {
+        if (obj_ids[d] < 0 || obj_ids[d] >= set->n)
+            return rfail(AAE_ERR_INVALID, "%s: draw %d names mesh %d of a set of %d", who, d, obj_ids[d], set->n);
+        if (scene_ids[d] < 0 || scene_ids[d] >= n_scenes)
+            return rfail(AAE_ERR_INVALID, "%s: draw %d names scene %d of %d", who, d, scene_ids[d], n_scenes);
+        a.draws.obj[d] = (uint16_t)obj_ids[d];
+        a.draws.scene[d] = (uint16_t)scene_ids[d];
+    }
+    const SceneLayout l = scene_layout(set->Vmax, set->Fmax, n_draws, n_scenes, p->W, p->H);
+    if (ws_bytes < l.total) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    if (((uintptr_t)ws & 255) != 0) return rfail(AAE_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+
+    hipStream_t stream = (hipStream_t)stream_;
+    char* base = (char*)ws;
+    a.meshes = set->table;
+    a.Vmax = set->Vmax; a.Fmax = set->Fmax;
+    a.Rs = Rs; a.ts = ts;
+    a.cam.K00 = p->K[0]; a.cam.K01 = p->K[1]; a.cam.K02 = p->K[2]; a.cam.K11 = p->K[4]; a.cam.K12 = p->K[5];
+    a.cam.near_ = p->clip_near; a.cam.far_ = p->clip_far;
+    a.cam.W = p->W; a.cam.H = p->H;
+    a.light.pos[0] = p->light[0]; a.light.pos[1] = p->light[1]; a.light.pos[2] = p->light[2];
+    a.light.ambient = p->ambient; a.light.diffuse = p->diffuse; a.light.specular = p->specular;
+    a.n_draws = n_draws; a.n_scenes = n_scenes;
+    a.rect = (int32_t*)(base + l.rect);
+    a.bounds = (int32_t*)(base + l.bounds);
+    a.raster_blocks = scene_raster_blocks(set->Fmax);
+    a.draw_obj = (int32_t*)(base + l.draw_obj);
+    a.vtx = (RcVertex*)(base + l.vtx);
+    a.vary = (float*)(base + l.vary);
+    a.keys = (unsigned long long*)(base + l.keys);
+
+    hipEvent_t ev[7] = {};
+    if (kernel_ms)
+        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
+    int stage = 0;
+#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
+    const bool cad = set->model == AAE_MODEL_CAD;
+    const dim3 block(RENDER_BLOCK);
+    const int n_init = n_draws > n_scenes ? n_draws : n_scenes;
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(scene_init, dim3((n_init + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    const dim3 vgrid((set->Vmax + RENDER_BLOCK - 1) / RENDER_BLOCK, n_draws);
+    if (cad) AAE_LAUNCH(scene_vertex<true>, vgrid, block, 0, stream, a);
+    else AAE_LAUNCH(scene_vertex<false>, vgrid, block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(scene_clear, dim3(RENDER_CLEAR_BLOCKS, n_scenes), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(scene_raster, dim3(a.raster_blocks, n_draws), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(scene_bbox, dim3(n_draws), dim3(64), 0, stream, a, bbs_out, visible_out);
+    AAE_RENDER_MARK();
+    const dim3 fgrid((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n_scenes);
+    if (cad) AAE_LAUNCH(scene_frame<true>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, draw_out, tri_out);
+    else AAE_LAUNCH(scene_frame<false>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, draw_out, tri_out);
+    AAE_RENDER_MARK();
+#undef AAE_RENDER_MARK
+    AAE_RENDER_TRY(hipGetLastError());
+    if (kernel_ms) {
+        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
+        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
+        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
+    }
+    return AAE_OK;
+}
+
 }  // namespace aae_render
 
 extern "C" {
@@ -209,6 +322,82 @@ int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, 
     if (!bgr_out || !depth_out) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_frames: null argument");
     return aae_render::render_run(mesh, Rs, ts, n, params, 0, nullptr, bgr_out, depth_out, tri_out, bbs_out, visible_out, workspace, ws_bytes,
                                   stream, nullptr, "aae_render_frames");
+}
+
+int aae_mesh_set_create(const aae_mesh* const* meshes, int n_meshes, aae_mesh_set** out) {
+    using namespace aae_render;
+    if (!meshes || !out) return rfail(AAE_ERR_INVALID, "aae_mesh_set_create: null argument");
+    if (n_meshes < 1 || n_meshes > AAE_SCENE_MAX_MESHES)
+        return rfail(AAE_ERR_UNSUPPORTED, "aae_mesh_set_create: %d meshes outside [1,%d]", n_meshes, AAE_SCENE_MAX_MESHES);
+    std::vector<SceneMesh> rows((size_t)n_meshes);
+    aae_mesh_set* set = new aae_mesh_set();
+    set->n = n_meshes;
+    for (int i = 0; i < n_meshes; ++i) {
+        const aae_mesh* m = meshes[i];
+        if (!m) {
+            delete set;
+            return rfail(AAE_ERR_INVALID, "aae_mesh_set_create: mesh %d is null", i);
+        }
+        if (i == 0) set->model = m->model;
+        if (m->model != set->model) {
+            delete set;
+            return rfail(AAE_ERR_UNSUPPORTED, "aae_mesh_set_create: mesh %d is of model kind %d, mesh 0 of kind %d (one kind per set)", i, m->model, set->model);
+        }
+        rows[i].verts = m->verts; rows[i].normals = m->normals; rows[i].colors = m->colors; rows[i].faces = m->faces;
+        rows[i].V = m->V; rows[i].F = m->F;
+        set->Vmax = m->V > set->Vmax ? m->V : set->Vmax;
+        set->Fmax = m->F > set->Fmax ? m->F : set->Fmax;
+    }
+    hipError_t e = hipMalloc((void**)&set->table, rows.size() * sizeof(SceneMesh));
+    if (e == hipSuccess) e = hipMemcpy(set->table, rows.data(), rows.size() * sizeof(SceneMesh), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        aae_mesh_set_destroy(set);
+        return rfail(AAE_ERR_RUNTIME, "aae_mesh_set_create: %s", hipGetErrorString(e));
+    }
+    *out = set;
+    return AAE_OK;
+}
+
+void aae_mesh_set_destroy(aae_mesh_set* set) {
+    if (!set) return;
+    if (set->table) (void)hipFree(set->table);
+    delete set;
+}
+
+size_t aae_render_scenes_workspace_bytes(const aae_mesh_set* set, int n_draws, int n_scenes, int W, int H) {
+    if (!set || n_draws < 1 || n_scenes < 1 || W < 1 || H < 1) return 0;
+    return aae_render::scene_layout(set->Vmax, set->Fmax, n_draws, n_scenes, W, H).total;
+}
+
+int aae_render_scenes(const aae_mesh_set* set, const int32_t* obj_ids, const int32_t* scene_ids, const double* Rs, const double* ts,
+                      int n_draws, int n_scenes, const aae_render_params* params, void* bgr_out, float* depth_out,
+                      int32_t* draw_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out,
+                      void* workspace, size_t ws_bytes, void* stream) {
+    return aae_render::scene_run(set, obj_ids, scene_ids, Rs, ts, n_draws, n_scenes, params, bgr_out, depth_out, draw_out, tri_out, bbs_out,
+                                 visible_out, workspace, ws_bytes, stream, nullptr, "aae_render_scenes");
+}
+
+int aae_render_scenes_timed(const aae_mesh_set* set, const int32_t* obj_ids, const int32_t* scene_ids, const double* Rs, const double* ts,
+                            int n_draws, int n_scenes, const aae_render_params* params, void* bgr_out, float* depth_out,
+                            int32_t* draw_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out,
+                            void* workspace, size_t ws_bytes, void* stream, float* kernel_ms) {
+    if (!kernel_ms) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_scenes_timed: null argument");
+    return aae_render::scene_run(set, obj_ids, scene_ids, Rs, ts, n_draws, n_scenes, params, bgr_out, depth_out, draw_out, tri_out, bbs_out,
+                                 visible_out, workspace, ws_bytes, stream, kernel_ms, "aae_render_scenes_timed");
+}
+
+int aae_overlay_blend(const void* image, const void* render, size_t n_pixels, int channel, void* out, void* stream) {
+    using namespace aae_render;
+    if (!image || !render || !out) return rfail(AAE_ERR_INVALID, "aae_overlay_blend: null argument");
+    if (channel < 0 || channel > 2) return rfail(AAE_ERR_INVALID, "aae_overlay_blend: channel %d outside [0,2]", channel);
+    if (n_pixels == 0) return AAE_OK;
+    const size_t n_bytes = n_pixels * 3;
+    const size_t blocks = (n_bytes + RENDER_BLOCK - 1) / RENDER_BLOCK;
+    if (blocks > 0x7FFFFFFFull) return rfail(AAE_ERR_UNSUPPORTED, "aae_overlay_blend: %zu pixels are too many for one launch", n_pixels);
+    AAE_LAUNCH(overlay_blend, dim3((unsigned)blocks), dim3(RENDER_BLOCK), 0, (hipStream_t)stream, (const uint8_t*)image, (const uint8_t*)render,
+               n_bytes, channel, (uint8_t*)out);
+    AAE_RENDER_TRY(hipGetLastError());
+    return AAE_OK;
 }
 
 }  // extern "C"

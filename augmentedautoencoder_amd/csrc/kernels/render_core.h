@@ -1,5 +1,6 @@
 // The mesh rasteriser's per-vertex, per-triangle and per-fragment functions as plain inline C++: the kernels of
-// render_raster.h call them on the device, tests/native/render_host.cpp calls the same text from serial loops on the host.
+// render_raster.h and render_scene.h call them on the device, tests/native/render_host.cpp and scene_host.cpp call the same
+// text from serial loops on the host.
 //
 // What they restate (paths relative to the reference's auto_pose/meshrenderer/):
 //   camera      gl_utils/camera.py:86-98,139-166 (realCamera + setIntrinsic: OpenCV extrinsics, z flipped into GL eye space)
@@ -281,6 +282,59 @@ RC_HD int32_t rc_nearest_src(int32_t d, int32_t dst, int32_t src) {
     const double inv = 1.0 / ((double)dst / (double)src);
     const int32_t s = (int32_t)floor((double)d * inv);
     return s < src - 1 ? s : src - 1;
+}
+
+// ---- scenes: several draws into one frame ------------------------------------------------------------------------------
+// A draw is (mesh of a set, R, t, scene); the draws of one scene share one key buffer.  Within a draw nothing changes: the
+// key's high word is still the fp32 bits of z.  The low word becomes draw * fmax + triangle (fmax: the largest face count of
+// the set, draw: the draw's index in the call's arrays), so at equal fp32 depth the earlier draw wins, then the lower
+// triangle: GL_LESS with the first-drawn fragment kept, whatever order the draws are rasterised in.
+RC_HD bool rc_scene_fits(uint64_t n_draws, uint64_t fmax) { return n_draws * fmax <= 0xFFFFFFFFull; }      // 0 <= both < 2^32
+
+RC_HD uint32_t rc_scene_index(uint32_t draw, uint32_t fmax, uint32_t tri) { return draw * fmax + tri; }
+
+RC_HD void rc_scene_decode(uint64_t key, uint32_t fmax, int32_t* draw, int32_t* tri) {
+    if (key == RC_BACKGROUND) {
+        *draw = -1; *tri = -1;
+        return;
+    }
+    const uint32_t low = (uint32_t)(key & 0xFFFFFFFFull);
+    *draw = (int32_t)(low / fmax);
+    *tri = (int32_t)(low % fmax);
+}
+
+// The box of a draw is calc_2d_bbox of the draw rendered alone (meshrenderer.py:172-183), not of its visible part: the
+// extremes of the pixels of its fragments (rc_fragment_key true), taken before the depth comparison.
+struct RcBounds {
+    int32_t x0, y0, x1, y1;                       // empty when x0 > x1
+};
+
+RC_HD void rc_bounds_empty(RcBounds* b) { b->x0 = INT32_MAX; b->y0 = INT32_MAX; b->x1 = INT32_MIN; b->y1 = INT32_MIN; }
+
+RC_HD void rc_bounds_add(RcBounds* b, int32_t px, int32_t py) {
+    b->x0 = px < b->x0 ? px : b->x0; b->y0 = py < b->y0 ? py : b->y0;
+    b->x1 = px > b->x1 ? px : b->x1; b->y1 = py > b->y1 ? py : b->y1;
+}
+
+// bounds -> (x, y, w, h), visible; a draw that covers no pixel gets box 0 and flag 0
+RC_HD void rc_bounds_box(const RcBounds& b, int32_t W, int32_t H, int32_t* bb, int32_t* visible) {
+    if (b.x0 > b.x1) {
+        bb[0] = bb[1] = bb[2] = bb[3] = 0;
+        *visible = 0;
+    } else {
+        rc_bbox(b.x0, b.y0, b.x1, b.y1, W, H, bb);
+        *visible = 1;
+    }
+}
+
+// ---- overlay ---------------------------------------------------------------------------------------------------------------
+// One byte of visualization/render_pose.py:44-46: image_show[bgr > 0] = g_y[bgr > 0]*2./3. + image_show[bgr > 0]*1./3. assigned
+// into a uint8 array; g_y holds the render's `channel` and 0 elsewhere.  NumPy's float64 operations in NumPy's order, then the
+// truncating cast.
+RC_HD uint8_t rc_overlay(uint8_t render, uint8_t image, bool in_channel) {
+    if (render == 0) return image;
+    const double g = in_channel ? (double)render : 0.0;
+    return (uint8_t)(g * 2. / 3. + (double)image * 1. / 3.);
 }
 
 }  // namespace aae_render

@@ -104,14 +104,17 @@ __global__ void __launch_bounds__(RENDER_BLOCK) render_vertex(RenderArgs a) {
 }
 
 // the view's rectangle, or an empty one (w == 0) when no usable vertex set it
-__device__ inline void load_rect(const RenderArgs& a, int view, int* x0, int* y0, int* w, int* h) {
-    const int32_t* r = a.rect + (size_t)view * 4;
+__device__ inline void rect_of(const int32_t* r, int W, int H, int* x0, int* y0, int* w, int* h) {
     const int rx0 = r[0], ry0 = r[1], rx1 = r[2], ry1 = r[3];
-    const bool ok = rx0 >= 0 && ry0 >= 0 && rx1 < a.cam.W && ry1 < a.cam.H && rx0 <= rx1 && ry0 <= ry1;
+    const bool ok = rx0 >= 0 && ry0 >= 0 && rx1 < W && ry1 < H && rx0 <= rx1 && ry0 <= ry1;
     *x0 = ok ? rx0 : 0;
     *y0 = ok ? ry0 : 0;
     *w = ok ? rx1 - rx0 + 1 : 0;
     *h = ok ? ry1 - ry0 + 1 : 0;
+}
+
+__device__ inline void load_rect(const RenderArgs& a, int view, int* x0, int* y0, int* w, int* h) {
+    rect_of(a.rect + (size_t)view * 4, a.cam.W, a.cam.H, x0, y0, w, h);
 }
 
 __global__ void __launch_bounds__(RENDER_BLOCK) render_clear(RenderArgs a) {
@@ -126,19 +129,26 @@ __global__ void __launch_bounds__(RENDER_BLOCK) render_clear(RenderArgs a) {
     }
 }
 
-__device__ inline void load_tri(const RenderArgs& a, int view, int tri, RcTri* T) {
-    const int32_t* f = a.faces + (size_t)tri * 3;
-    const RcVertex* vv = a.vtx + (size_t)view * a.V;
+// triangle `tri` of a face list, from the snapped vertices vv of its view (scenes: of its draw)
+__device__ inline void tri_of(const int32_t* faces, const RcVertex* vv, int tri, int W, int H, RcTri* T) {
+    const int32_t* f = faces + (size_t)tri * 3;
     const RcVertex v0 = vv[f[0]], v1 = vv[f[1]], v2 = vv[f[2]];
-    rc_tri_setup(v0, v1, v2, a.cam.W, a.cam.H, T);
+    rc_tri_setup(v0, v1, v2, W, H, T);
 }
 
-__device__ inline void raster_pixel(const RcTri& T, int x, int y, double far_, unsigned tri, unsigned long long* keys, int W) {
+__device__ inline void load_tri(const RenderArgs& a, int view, int tri, RcTri* T) {
+    tri_of(a.faces, a.vtx + (size_t)view * a.V, tri, a.cam.W, a.cam.H, T);
+}
+
+// true when the pixel holds a fragment of the triangle (covered, not beyond the far plane), whether or not it is visible
+__device__ inline bool raster_pixel(const RcTri& T, int x, int y, double far_, unsigned tri, unsigned long long* keys, int W) {
     uint64_t key;
     if (rc_fragment_key(T, x, y, far_, tri, &key)) {
         unsigned long long* k = keys + (size_t)y * W + x;
         if ((unsigned long long)key < *k) atomicMin(k, (unsigned long long)key);      // keys only ever decrease: the plain read is a filter
+        return true;
     }
+    return false;
 }
 
 __global__ void __launch_bounds__(RENDER_BLOCK) render_raster(RenderArgs a) {
@@ -217,14 +227,20 @@ __device__ inline unsigned long long key_at(const RenderArgs& a, int view, int x
     return a.keys[((size_t)view * a.cam.H + y) * a.cam.W + x];
 }
 
+// colour of the fragment of triangle `tri` at (x, y): vv / vb are the snapped vertices and varyings of its view (draw)
+template <bool CAD>
+__device__ inline void shade_of(const int32_t* faces, const float* colors, const RcVertex* vv, const float* vb, unsigned tri, int x, int y,
+                                int W, int H, const RcLight& light, uint8_t* bgr) {
+    RcTri T;
+    tri_of(faces, vv, (int)tri, W, H, &T);
+    const int32_t* f = faces + (size_t)tri * 3;
+    rc_shade<CAD>(T, x, y, vb + (size_t)f[0] * RC_VARY, vb + (size_t)f[1] * RC_VARY, vb + (size_t)f[2] * RC_VARY,
+                  colors + (size_t)f[0] * 3, colors + (size_t)f[1] * 3, colors + (size_t)f[2] * 3, light, bgr);
+}
+
 template <bool CAD>
 __device__ inline void shade_pixel(const RenderArgs& a, int view, unsigned tri, int x, int y, uint8_t* bgr) {
-    RcTri T;
-    load_tri(a, view, (int)tri, &T);
-    const int32_t* f = a.faces + (size_t)tri * 3;
-    const float* vb = a.vary + (size_t)view * a.V * RC_VARY;
-    rc_shade<CAD>(T, x, y, vb + (size_t)f[0] * RC_VARY, vb + (size_t)f[1] * RC_VARY, vb + (size_t)f[2] * RC_VARY,
-                  a.colors + (size_t)f[0] * 3, a.colors + (size_t)f[1] * 3, a.colors + (size_t)f[2] * 3, a.light, bgr);
+    shade_of<CAD>(a.faces, a.colors, a.vtx + (size_t)view * a.V, a.vary + (size_t)view * a.V * RC_VARY, tri, x, y, a.cam.W, a.cam.H, a.light, bgr);
 }
 
 template <bool CAD>

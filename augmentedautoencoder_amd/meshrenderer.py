@@ -4,7 +4,7 @@
 computed and how exactly), plus the PLY reader the reference loads its models with.
 
 No OpenGL, EGL or pyassimp: the mesh is uploaded once (``aae_mesh_create``) and every call renders a batch of views
-in six launches.  Parity with a real OpenGL driver is unpinned; the geometry is reproducible bit for bit against the
+in six launches; ``render_many`` / ``render_scenes`` draw several models into one frame (``aae_render_scenes``).  Parity with a real OpenGL driver is unpinned; the geometry is reproducible bit for bit against the
 float64 restatement of the tests."""
 from __future__ import annotations
 
@@ -184,6 +184,7 @@ class Renderer(object):
         self._arrays = [mesh_arrays(p if isinstance(p, dict) else load_ply(p), model) for p in models_cad_files]
         self._device = device
         self._meshes = None
+        self._set = None
         self._ws = None
         self.lib = None
 
@@ -205,11 +206,19 @@ class Renderer(object):
                                               MODEL_KINDS[self.model], self.vertex_scale, ctypes.byref(h))
                 _lib.check(self.lib, rc, 'aae_mesh_create')
                 meshes.append(h)
-        self._meshes = meshes
+            self._meshes = meshes
+            # the set of all models (render_scenes / render_many): a device table of the mesh descriptors, written once
+            handles = (ctypes.c_void_p * len(meshes))(*[h.value for h in meshes])
+            mesh_set = ctypes.c_void_p()
+            rc = self.lib.aae_mesh_set_create(handles, len(meshes), ctypes.byref(mesh_set))
+            if rc != _lib.AAE_OK:
+                self.close()
+            _lib.check(self.lib, rc, 'aae_mesh_set_create')
+            self._set = mesh_set
 
-    def _workspace(self, mesh, n, W, H):
+    def _workspace(self, mesh, n, W, H, need=None):
         import torch
-        need = int(self.lib.aae_render_workspace_bytes(mesh, n, W, H))
+        need = int(self.lib.aae_render_workspace_bytes(mesh, n, W, H)) if need is None else int(need)
         if self._ws is None or self._ws.numel() - (-self._ws.data_ptr()) % 256 < need:
             self._ws = None
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self._device)
@@ -293,7 +302,93 @@ class Renderer(object):
                                              np.asarray(t, dtype=np.float64).reshape(3), near, far, random_light, phong)
         return bgr[0].cpu().numpy(), depth[0].cpu().numpy()
 
+    def render_scenes(self, obj_ids, scene_ids, n_scenes, W, H, K, Rs, ts, near, far, random_light=False, phong=None, workspace=None,
+                      return_ids=False, timed=False):
+        """Several models into one frame, several frames in one call: draw d is model obj_ids[d] at (Rs[d], ts[d]) in scene
+        scene_ids[d] -> (bgr uint8 [S,H,W,3], depth float32 [S,H,W], obj_bbs int32 [D,4], visible int32 [D]) as device tensors,
+        with return_ids=True also the winning draw and its face per pixel (int32 [S,H,W], -1 = background); with timed=True also
+        the milliseconds of the six launches.  The draws of a scene share one depth buffer: the nearest fp32 depth wins, at
+        equal depth the earlier draw.  obj_bbs[d] is the box of draw d rendered alone (render_many's), visible[d] = 0 when it
+        covers no pixel.  One light for the call.  At most 256 draws a call: split by scene."""
+        import torch
+        self._open()
+        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
+        W, H, S = int(W), int(H), int(n_scenes)
+        obj = np.ascontiguousarray(np.asarray(obj_ids, dtype=np.int32).reshape(-1))
+        scn = np.ascontiguousarray(np.asarray(scene_ids, dtype=np.int32).reshape(-1))
+        D = len(obj)
+        if D > _lib.AAE_SCENE_MAX_DRAWS:
+            raise ValueError('aae_render_scenes: %d draws, at most %d per call (split by scene)' % (D, _lib.AAE_SCENE_MAX_DRAWS))
+        if D < 1 or len(scn) != D:
+            raise ValueError('aae_render_scenes: %d obj_ids, %d scene_ids' % (D, len(scn)))
+        if S < 1:
+            raise ValueError('aae_render_scenes: %d scenes' % S)
+        Rd, td = self._upload(Rs, 9), self._upload(ts, 3)
+        if Rd.shape[0] != D or td.shape[0] != D:
+            raise ValueError('aae_render_scenes: %d draws, %d rotations, %d translations' % (D, Rd.shape[0], td.shape[0]))
+        light, a, d, s = draw_light(random_light, phong, self.model)
+        p = render_params(W, H, K, None, near, far, 1.0, light, a, d, s)
+        with torch.cuda.device(self._device):
+            bgr = torch.empty((S, H, W, 3), dtype=torch.uint8, device=self._device)
+            depth = torch.empty((S, H, W), dtype=torch.float32, device=self._device)
+            bbs = torch.empty((D, 4), dtype=torch.int32, device=self._device)
+            vis = torch.empty((D,), dtype=torch.int32, device=self._device)
+            draw = torch.empty((S, H, W), dtype=torch.int32, device=self._device) if return_ids else None
+            tri = torch.empty((S, H, W), dtype=torch.int32, device=self._device) if return_ids else None
+            if workspace is not None:
+                ws_ptr, ws_bytes = workspace
+            else:
+                ws_ptr, ws_bytes = self._workspace(None, D, W, H, need=self.lib.aae_render_scenes_workspace_bytes(self._set, D, S, W, H))
+            args = (self._set, obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                    ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(td.data_ptr()), D, S, ctypes.byref(p), ctypes.c_void_p(bgr.data_ptr()),
+                    ctypes.c_void_p(depth.data_ptr()), ctypes.c_void_p(draw.data_ptr()) if return_ids else None,
+                    ctypes.c_void_p(tri.data_ptr()) if return_ids else None, ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()),
+                    ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
+            if timed:
+                ms = (ctypes.c_float * 6)()
+                _lib.check(self.lib, self.lib.aae_render_scenes_timed(*(args + (ms,))), 'aae_render_scenes_timed')
+            else:
+                _lib.check(self.lib, self.lib.aae_render_scenes(*args), 'aae_render_scenes')
+        out = (bgr, depth, bbs, vis) + ((draw, tri) if return_ids else ())
+        return out + (list(ms),) if timed else out
+
+    def render_many(self, obj_ids, W, H, K, Rs, ts, near, far, random_light=None, phong=None):
+        """meshrenderer.py:140-194 / meshrenderer_phong.py:170-224: the models obj_ids at the poses (Rs[i], ts[i]) in one frame with
+        one depth buffer -> (bgr uint8 [H,W,3], depth float32 [H,W], bbs: one [x, y, w, h] per object, of the object rendered
+        alone) on the host.  random_light=None is the reference's default for the kind (True for 'reconst', False for 'cad');
+        the light is drawn once per call.  A draw that covers no pixel raises ValueError (the reference: from calc_2d_bbox)."""
+        if random_light is None:
+            random_light = self.model == 'reconst'
+        n = len(obj_ids)
+        bgr, depth, bbs, vis = self.render_scenes(obj_ids, [0] * n, 1, W, H, K, np.asarray([np.asarray(R, dtype=np.float64).reshape(3, 3) for R in Rs]),
+                                                  np.asarray([np.asarray(t, dtype=np.float64).reshape(3) for t in ts]), near, far, random_light, phong)
+        vis = vis.cpu().numpy()
+        for i in range(n):
+            if not vis[i]:
+                raise ValueError('render_many: draw %d (obj_id %d) covers no pixel of the %dx%d frame' % (i, int(obj_ids[i]), int(W), int(H)))
+        return bgr[0].cpu().numpy(), depth[0].cpu().numpy(), [[int(v) for v in bb] for bb in bbs.cpu().numpy()]
+
+    def overlay_blend(self, image, render, channel=1, out=None):
+        """aae_overlay_blend on device uint8 tensors of one shape [..., 3]: where render > 0, two thirds of the render's `channel`
+        over one third of the image (visualization/render_pose.py:44-46); out may be image itself."""
+        import torch
+        self._open()
+        if image.shape != render.shape or image.dtype != torch.uint8 or render.dtype != torch.uint8 or image.shape[-1] != 3:
+            raise ValueError('aae_overlay_blend: image %s %s, render %s %s' % (tuple(image.shape), image.dtype, tuple(render.shape), render.dtype))
+        image, render = image.contiguous(), render.contiguous()
+        out = torch.empty_like(image) if out is None else out
+        if not out.is_contiguous() or out.shape != image.shape or out.dtype != torch.uint8:
+            raise ValueError('aae_overlay_blend: out must be a contiguous uint8 tensor of the image\'s shape')
+        with torch.cuda.device(self._device):
+            rc = self.lib.aae_overlay_blend(ctypes.c_void_p(image.data_ptr()), ctypes.c_void_p(render.data_ptr()), image.numel() // 3, int(channel),
+                                            ctypes.c_void_p(out.data_ptr()), self._stream())
+        _lib.check(self.lib, rc, 'aae_overlay_blend')
+        return out
+
     def close(self):
+        if self._set is not None:
+            self.lib.aae_mesh_set_destroy(self._set)
+        self._set = None
         if self._meshes is not None:
             for h in self._meshes:
                 self.lib.aae_mesh_destroy(h)

@@ -393,6 +393,43 @@ int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, 
                       void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* Several meshes into one frame: Renderer.render_many (meshrenderer.py:140-194, meshrenderer_phong.py:170-224), which
+ * PoseVisualizer.render_poses (visualization/render_pose.py) and the multi-object demos end in.  A draw is (mesh of a set, R, t,
+ * scene); the draws of one scene share one depth buffer.  Per draw the fragments are those of aae_render_frames for that mesh and
+ * pose alone; across draws the nearest fp32 depth wins, at equal depth the earlier draw of the call's arrays, then the lower face
+ * (GL_LESS, the first-drawn fragment kept).  The box of a draw is calc_2d_bbox of the draw rendered alone, as render_many
+ * returns it, not the box of its visible part.  One light and one set of Phong constants per call. */
+typedef struct aae_mesh_set aae_mesh_set;
+/* borrows the meshes (they must outlive the set); all of one model kind, else AAE_ERR_UNSUPPORTED; allocation happens here */
+int aae_mesh_set_create(const aae_mesh* const* meshes, int n_meshes, aae_mesh_set** out);
+void aae_mesh_set_destroy(aae_mesh_set* set);
+
+#define AAE_SCENE_MAX_DRAWS 256   /* the (mesh, scene) table of a call travels in the kernel arguments               */
+size_t aae_render_scenes_workspace_bytes(const aae_mesh_set* set, int n_draws, int n_scenes, int W, int H);
+
+/* obj_ids, scene_ids: HOST int32 [n_draws], validated here (0 <= obj < meshes of the set, 0 <= scene < n_scenes; any order;
+ * a scene without draws is all background).  Rs device float64 [n_draws,9], ts device float64 [n_draws,3] (required; params->t
+ * and pad_factor are not read).  bgr_out device uint8 [n_scenes,H,W,3], depth_out device float32 [n_scenes,H,W] (0 = background),
+ * draw_out / tri_out device int32 [n_scenes,H,W] or NULL (-1 = background), bbs_out device int32 [n_draws,4], visible_out
+ * device int32 [n_draws] (0: the draw covers no pixel, its box is 0).  n_draws <= AAE_SCENE_MAX_DRAWS, n_scenes <= 65535,
+ * n_draws * (largest face count of the set) <= 2^32 - 1.  The workspace may hold anything on entry; no allocation, no
+ * synchronisation, no copy from host memory: capturable into a graph. */
+int aae_render_scenes(const aae_mesh_set* set, const int32_t* obj_ids, const int32_t* scene_ids, const double* Rs, const double* ts,
+                      int n_draws, int n_scenes, const aae_render_params* params, void* bgr_out, float* depth_out,
+                      int32_t* draw_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out,
+                      void* workspace, size_t ws_bytes, void* stream);
+/* the same call with the time of each of its six launches (init, vertex, clear, raster, bbox, frame) from events on `stream`;
+ * synchronises, so not for capture */
+int aae_render_scenes_timed(const aae_mesh_set* set, const int32_t* obj_ids, const int32_t* scene_ids, const double* Rs, const double* ts,
+                            int n_draws, int n_scenes, const aae_render_params* params, void* bgr_out, float* depth_out,
+                            int32_t* draw_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out,
+                            void* workspace, size_t ws_bytes, void* stream, float* kernel_ms);
+
+/* The blend of visualization/render_pose.py:44-46, device uint8 buffers of n_pixels*3 bytes:
+ * out[e] = render[e] > 0 ? (uint8)((render[e] * (e % 3 == channel)) * 2./3. + image[e] * 1./3.) : image[e], in float64 as NumPy
+ * computes it; out may alias image */
+int aae_overlay_blend(const void* image, const void* render, size_t n_pixels, int channel, void* out, void* stream);
+
 /* ---- Depth ICP refinement ---------------------------------------------------------------------------
  * Replaces icp_refinement's point clouds, filter and ICP loop (auto_pose/eval/icp_utils.py:96-175,248-274 and the
  * same code in auto_pose/icp/icp.py) for up to AAE_ICP_MAX_PROBLEMS detections per call, all in float64
