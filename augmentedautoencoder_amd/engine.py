@@ -877,12 +877,26 @@ class DecoderEngine(object):
             return [(self.lib.aae_decoder_kernel_label(self.handle, i).decode(), float(ms[i]),
                      float(self.lib.aae_decoder_kernel_flops(self.handle, i))) for i in range(n.value)]
 
-    def decode(self, z):
-        """Decoder.x: device float32 [B,H,W,C] in [0,1]."""
+    def decode(self, z, out=None):
+        """Decoder.x: device float32 [B,H,W,C] in [0,1].  out: the caller's tensor to decode into (contiguous float32
+        [B,H,W,C] on the engine's device; returned) -- every element of it is written."""
         torch = _torch()
         z = self._z(z)
         B = z.shape[0]
-        out = torch.empty((B,) + tuple(self.cfg.shape), dtype=torch.float32, device=self.device)
+        shape = (B,) + tuple(self.cfg.shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            if not isinstance(out, torch.Tensor):
+                raise ValueError('out must be a torch tensor, got %s' % type(out).__name__)
+            if tuple(out.shape) != shape:
+                raise ValueError('out has shape %s, this call decodes into %s' % (tuple(out.shape), shape))
+            if out.dtype != torch.float32:
+                raise ValueError('out has dtype %s, the decoder writes float32' % out.dtype)
+            if out.device.type != self.device.type or (out.device.index or 0) != (self.device.index or 0):
+                raise ValueError('out lives on %s, the decoder on %s' % (out.device, self.device))
+            if not out.is_contiguous():
+                raise ValueError('out must be contiguous')
         for a in range(0, B, self.max_batch):
             e = min(a + self.max_batch, B)
             self._chunk(z[a:e], out[a:e])
