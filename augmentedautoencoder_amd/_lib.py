@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
     'aae_decoder_create', 'aae_decoder_destroy', 'aae_decoder_workspace_bytes', 'aae_decoder_forward',
     'aae_decoder_forward_timed', 'aae_decoder_kernel_label', 'aae_decoder_kernel_flops', 'aae_decoder_activation_info',
     'aae_mesh_create', 'aae_mesh_destroy', 'aae_render_workspace_bytes', 'aae_render_embedding_views', 'aae_render_embedding_views_timed',
-    'aae_render_frames',
+    'aae_render_frames', 'aae_render_training_workspace_bytes', 'aae_render_training_views', 'aae_render_training_views_timed',
     'aae_mesh_set_create', 'aae_mesh_set_destroy', 'aae_render_scenes_workspace_bytes', 'aae_render_scenes', 'aae_render_scenes_timed',
     'aae_overlay_blend',
     'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
@@ -227,6 +227,14 @@ def declare_render(lib):
     lib.aae_render_frames.restype = c_int
     lib.aae_render_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_int, POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]
+    lib.aae_render_training_workspace_bytes.restype = c_size_t
+    lib.aae_render_training_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    training = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(RenderParams), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_size_t, c_void_p]
+    lib.aae_render_training_views.restype = c_int
+    lib.aae_render_training_views.argtypes = training
+    lib.aae_render_training_views_timed.restype = c_int
+    lib.aae_render_training_views_timed.argtypes = training + [POINTER(c_float)]
     lib.aae_mesh_set_create.restype = c_int
     lib.aae_mesh_set_create.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p)]
     lib.aae_mesh_set_destroy.restype = None

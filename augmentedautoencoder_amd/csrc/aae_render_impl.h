@@ -12,6 +12,7 @@
 #include "../../include/aae_hip.h"
 #include "kernels/render_raster.h"
 #include "kernels/render_scene.h"
+#include "kernels/render_train.h"
 
 namespace aae_host {
 void set_last_error(const char* msg);          // aae_host_types.h: the thread's aae_last_error() text lives in aae_hip.hip
@@ -55,12 +56,12 @@ struct WsLayout {
     size_t rect, vtx, vary, keys, total;
 };
 
-static WsLayout ws_layout(int V, int n, int W, int H) {
+static WsLayout ws_layout(int V, int n, int W, int H, int n_vary = RC_VARY) {
     WsLayout l;
     size_t o = 0;
     l.rect = o; o += up256((size_t)n * 4 * sizeof(int32_t));
     l.vtx = o;  o += up256((size_t)n * V * sizeof(RcVertex));
-    l.vary = o; o += up256((size_t)n * V * RC_VARY * sizeof(float));
+    l.vary = o; o += up256((size_t)n * V * n_vary * sizeof(float));
     l.keys = o; o += up256((size_t)n * W * H * sizeof(unsigned long long));
     l.total = o;
     return l;
@@ -69,23 +70,21 @@ static WsLayout ws_layout(int V, int n, int W, int H) {
 #define AAE_RENDER_MAX_DIM 4096
 #define AAE_RENDER_MAX_VIEWS 65535           /* the view is blockIdx.y */
 
-// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
-static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, int crop,
-                      void* crops_out, void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes,
-                      void* stream_, float* kernel_ms, const char* who) {
-    if (!m || !Rs || !p || !bbs_out || !visible_out || !ws) return rfail(AAE_ERR_INVALID, "%s: null argument", who);
+// the checks every batch-of-views call makes after its null checks, in this order; crop: nullptr when the call cuts no patches
+static int check_views(int n, const aae_render_params* p, const int* crop, const WsLayout& l, const void* ws, size_t ws_bytes, const char* who) {
     if (n < 1 || n > AAE_RENDER_MAX_VIEWS) return rfail(AAE_ERR_UNSUPPORTED, "%s: %d views outside [1,%d] per call", who, n, AAE_RENDER_MAX_VIEWS);
     if (p->W < 1 || p->H < 1 || p->W > AAE_RENDER_MAX_DIM || p->H > AAE_RENDER_MAX_DIM)
         return rfail(AAE_ERR_UNSUPPORTED, "%s: render dims %dx%d outside [1,%d]", who, p->W, p->H, AAE_RENDER_MAX_DIM);
     if (p->K[3] != 0.0 || p->K[6] != 0.0 || p->K[7] != 0.0)
         return rfail(AAE_ERR_INVALID, "%s: K[1,0], K[2,0] and K[2,1] must be 0", who);
     if (!(p->clip_near > 0.0) || !(p->clip_far > p->clip_near)) return rfail(AAE_ERR_INVALID, "%s: need 0 < near < far", who);
-    if (crops_out && (crop < 1 || crop > AAE_RENDER_MAX_DIM)) return rfail(AAE_ERR_UNSUPPORTED, "%s: crop size %d outside [1,%d]", who, crop, AAE_RENDER_MAX_DIM);
-    const WsLayout l = ws_layout(m->V, n, p->W, p->H);
+    if (crop && (*crop < 1 || *crop > AAE_RENDER_MAX_DIM)) return rfail(AAE_ERR_UNSUPPORTED, "%s: crop size %d outside [1,%d]", who, *crop, AAE_RENDER_MAX_DIM);
     if (ws_bytes < l.total) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
     if (((uintptr_t)ws & 255) != 0) return rfail(AAE_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+    return AAE_OK;
+}
 
-    hipStream_t stream = (hipStream_t)stream_;
+static RenderArgs render_args(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, const WsLayout& l, void* ws) {
     char* base = (char*)ws;
     RenderArgs a;
     a.verts = m->verts; a.normals = m->normals; a.colors = m->colors; a.faces = m->faces;
@@ -102,6 +101,19 @@ static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int
     a.vtx = (RcVertex*)(base + l.vtx);
     a.vary = (float*)(base + l.vary);
     a.keys = (unsigned long long*)(base + l.keys);
+    return a;
+}
+
+// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, int crop,
+                      void* crops_out, void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes,
+                      void* stream_, float* kernel_ms, const char* who) {
+    if (!m || !Rs || !p || !bbs_out || !visible_out || !ws) return rfail(AAE_ERR_INVALID, "%s: null argument", who);
+    const WsLayout l = ws_layout(m->V, n, p->W, p->H);
+    if (int rc = check_views(n, p, crops_out ? &crop : nullptr, l, ws, ws_bytes, who)) return rc;
+
+    hipStream_t stream = (hipStream_t)stream_;
+    const RenderArgs a = render_args(m, Rs, ts, n, p, l, ws);
 
     hipEvent_t ev[7] = {};
     if (kernel_ms)
@@ -132,6 +144,57 @@ static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int
         if (cad) AAE_LAUNCH(render_frame<true>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
         else AAE_LAUNCH(render_frame<false>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
     }
+    AAE_RENDER_MARK();
+#undef AAE_RENDER_MARK
+    AAE_RENDER_TRY(hipGetLastError());
+    if (kernel_ms) {
+        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
+        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
+        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
+    }
+    return AAE_OK;
+}
+
+// a batch of training pairs: render_run's launches with the training forms of the vertex stage and the crop
+// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+static int train_run(const aae_mesh* m, const double* Rs, const float* lights, const double* offsets, int n, const aae_render_params* p, int crop,
+                     void* train_x, void* mask_x, void* train_y, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes, void* stream_,
+                     float* kernel_ms, const char* who) {
+    if (!m || !Rs || !lights || !offsets || !p || !train_x || !mask_x || !train_y || !bbs_out || !visible_out || !ws)
+        return rfail(AAE_ERR_INVALID, "%s: null argument", who);
+    const WsLayout l = ws_layout(m->V, n, p->W, p->H, RC_VARY_TRAIN);
+    if (int rc = check_views(n, p, &crop, l, ws, ws_bytes, who)) return rc;
+
+    hipStream_t stream = (hipStream_t)stream_;
+    const RenderArgs a = render_args(m, Rs, nullptr, n, p, l, ws);
+    TrainArgs ta;
+    ta.lights = lights; ta.offsets = offsets;
+
+    hipEvent_t ev[7] = {};
+    if (kernel_ms)
+        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
+    int stage = 0;
+#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
+    const bool cad = m->model == AAE_MODEL_CAD;
+    const dim3 block(RENDER_BLOCK);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_init_rect, dim3((n + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    const dim3 vgrid((m->V + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
+    if (cad) AAE_LAUNCH(render_vertex_train<true>, vgrid, block, 0, stream, a, ta);
+    else AAE_LAUNCH(render_vertex_train<false>, vgrid, block, 0, stream, a, ta);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_clear, dim3(RENDER_CLEAR_BLOCKS, n), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_raster, dim3((m->F + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a);
+    AAE_RENDER_MARK();
+    AAE_LAUNCH(render_bbox, dim3(n), block, 0, stream, a, bbs_out, visible_out);
+    AAE_RENDER_MARK();
+    const dim3 cgrid((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
+    if (cad) AAE_LAUNCH(render_train_crop<true>, cgrid, block, 0, stream, a, ta, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop,
+                        (uint8_t*)train_x, (uint8_t*)mask_x, (uint8_t*)train_y);
+    else AAE_LAUNCH(render_train_crop<false>, cgrid, block, 0, stream, a, ta, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop,
+                    (uint8_t*)train_x, (uint8_t*)mask_x, (uint8_t*)train_y);
     AAE_RENDER_MARK();
 #undef AAE_RENDER_MARK
     AAE_RENDER_TRY(hipGetLastError());
@@ -322,6 +385,26 @@ int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, 
     if (!bgr_out || !depth_out) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_frames: null argument");
     return aae_render::render_run(mesh, Rs, ts, n, params, 0, nullptr, bgr_out, depth_out, tri_out, bbs_out, visible_out, workspace, ws_bytes,
                                   stream, nullptr, "aae_render_frames");
+}
+
+size_t aae_render_training_workspace_bytes(const aae_mesh* mesh, int n_views, int W, int H) {
+    if (!mesh || n_views < 1 || W < 1 || H < 1) return 0;
+    return aae_render::ws_layout(mesh->V, n_views, W, H, RC_VARY_TRAIN).total;
+}
+
+int aae_render_training_views(const aae_mesh* mesh, const double* Rs, const float* lights, const double* offsets, int n,
+                              const aae_render_params* params, int crop, void* train_x, void* mask_x, void* train_y, int32_t* bbs_out,
+                              int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream) {
+    return aae_render::train_run(mesh, Rs, lights, offsets, n, params, crop, train_x, mask_x, train_y, bbs_out, visible_out, workspace, ws_bytes,
+                                 stream, nullptr, "aae_render_training_views");
+}
+
+int aae_render_training_views_timed(const aae_mesh* mesh, const double* Rs, const float* lights, const double* offsets, int n,
+                                    const aae_render_params* params, int crop, void* train_x, void* mask_x, void* train_y, int32_t* bbs_out,
+                                    int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream, float* kernel_ms) {
+    if (!kernel_ms) return aae_render::rfail(AAE_ERR_INVALID, "aae_render_training_views_timed: null argument");
+    return aae_render::train_run(mesh, Rs, lights, offsets, n, params, crop, train_x, mask_x, train_y, bbs_out, visible_out, workspace, ws_bytes,
+                                 stream, kernel_ms, "aae_render_training_views_timed");
 }
 
 int aae_mesh_set_create(const aae_mesh* const* meshes, int n_meshes, aae_mesh_set** out) {

@@ -1,12 +1,13 @@
 // The mesh rasteriser's per-vertex, per-triangle and per-fragment functions as plain inline C++: the kernels of
-// render_raster.h and render_scene.h call them on the device, tests/native/render_host.cpp and scene_host.cpp call the same
-// text from serial loops on the host.
+// render_raster.h, render_scene.h and render_train.h call them on the device, tests/native/render_host.cpp, scene_host.cpp and
+// train_host.cpp call the same text from serial loops on the host.
 //
 // What they restate (paths relative to the reference's auto_pose/meshrenderer/):
 //   camera      gl_utils/camera.py:86-98,139-166 (realCamera + setIntrinsic: OpenCV extrinsics, z flipped into GL eye space)
 //   reconst     shader/depth_shader_phong.vs, shader/depth_shader_phong.frag, meshrenderer_phong.py:41-60,101-168
 //   cad         shader/cad_shader.vs, shader/cad_shader.frag, meshrenderer.py:37-47,84-137
 //   bbox, crop  pysixd/view_sampler.py:10-15 (calc_2d_bbox), auto_pose/ae/dataset.py:354-373 (extract_square_patch)
+//   pairs       auto_pose/ae/dataset.py:238-303 (render_training_images: second light, shifted box)
 //
 // The exact-geometry rule.  Pixel coordinates are computed in float64, snapped to 1/256 pixel, and everything that decides
 // WHICH triangle a pixel shows is integer arithmetic on the snapped vertices or float64 arithmetic in one fixed order of
@@ -99,6 +100,27 @@ RC_HD void rc_vertex(const double* R, const double* t, const RcCamera& cam, cons
     vary[6] = (float)(ax / nl);
     vary[7] = (float)(ay / nl);
     vary[8] = (float)(az / nl);
+}
+
+// v_L of the same vertex under another light (training pairs: the view's own light next to the call's default one): the
+// float64 expressions of rc_vertex's v_L in their order, so a view rendered with that light alone has these three floats
+#define RC_VARY_TRAIN 12                          /* RC_VARY of the default light, then v_L of the view's light    */
+
+template <bool CAD>
+RC_HD void rc_light_dir(const double* R, const double* t, const RcLight& light, const float* p, float* vL) {
+    const double X = (double)p[0], Y = (double)p[1], Z = (double)p[2];
+    const double xc = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0];
+    const double yc = ((R[3] * X + R[4] * Y) + R[5] * Z) + t[1];
+    const double zc = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
+    const double Px = xc, Py = yc, Pz = -zc;
+    double Lx = (double)light.pos[0] - Px, Ly = (double)light.pos[1] - Py, Lz = (double)light.pos[2] - Pz;
+    if (!CAD) {
+        const double ll = sqrt(Lx * Lx + Ly * Ly + Lz * Lz);
+        Lx /= ll; Ly /= ll; Lz /= ll;
+    }
+    vL[0] = (float)Lx;
+    vL[1] = (float)Ly;
+    vL[2] = (float)Lz;
 }
 
 // pixel columns (rows) whose sample can lie inside a triangle that has a vertex at snapped coordinate c: the screen
@@ -274,6 +296,31 @@ RC_HD void rc_crop_rect(const int32_t* bb, double pad_factor, int32_t W, int32_t
     *right = (int32_t)fmin(cx + hs, (double)W);
     *top = (int32_t)fmax(cy - hs, 0.0);
     *bottom = (int32_t)fmin(cy + hs, (double)H);
+}
+
+// The shifted box of a training image (dataset.py:282-285, 356): obj_bb + [u_x w, u_y h, 0, 0] in float64, then
+// .astype(np.int32), which truncates toward zero; w and h stay.  Its source rectangle is rc_crop_rect of the result.
+RC_HD void rc_offset_box(const int32_t* bb, double ux, double uy, int32_t* out) {
+    out[0] = (int32_t)((double)bb[0] + ux * (double)bb[2]);
+    out[1] = (int32_t)((double)bb[1] + uy * (double)bb[3]);
+    out[2] = bb[2];
+    out[3] = bb[3];
+}
+
+// rc_shade of a fragment under the view's own light: tv0..2 are the RC_VARY_TRAIN floats of the three vertices; rc_shade gets
+// copies of their varyings with v_L replaced, so the bytes are those of a render with that light alone
+template <bool CAD>
+RC_HD void rc_shade_relit(const RcTri& T, int32_t px, int32_t py, const float* tv0, const float* tv1, const float* tv2,
+                          const float* col0, const float* col1, const float* col2, const RcLight& light, uint8_t* bgr) {
+    float v0[RC_VARY], v1[RC_VARY], v2[RC_VARY];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int k = 0; k < RC_VARY; ++k) {
+        const int s = (k >= 3 && k < 6) ? k + 6 : k;
+        v0[k] = tv0[s]; v1[k] = tv1[s]; v2[k] = tv2[s];
+    }
+    rc_shade<CAD>(T, px, py, v0, v1, v2, col0, col1, col2, light, bgr);
 }
 
 // cv2.resize(INTER_NEAREST): OpenCV modules/imgproc/src/resize.cpp, resizeNN: x_ofs[x] = min(cvFloor(x * ifx), ssize.width - 1)

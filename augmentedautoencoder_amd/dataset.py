@@ -1,15 +1,17 @@
-"""The slice of ``Dataset`` (/root/reference/auto_pose/ae/dataset.py) that the
-inference hot path touches: the cfg keyword bag, the crop shape, the
-codebook-row -> rotation table, and the hook through which update_embedding
-obtains the views to embed.
+"""The slice of ``Dataset`` (the reference's auto_pose/ae/dataset.py) that starts from a mesh and a cfg: the cfg keyword bag,
+the crop shape, the codebook-row -> rotation table, the hook through which update_embedding obtains the views to embed, and
+the training set (``get_training_images`` / ``render_training_images``: the ``<md5>.npz`` the reference's ``ae_train``
+looks for first).
 
-Augmentation and training-set generation are out of scope (SURVEY.md section 2,
-rows 5 and 10).  ``render_embedding_image_batch`` delegates to a pluggable *view
-source*; ``MeshViewSource`` is the one that renders the object's mesh on the GPU
-(meshrenderer.py, the HIP rasteriser) in place of the reference's OpenGL context.
+``render_embedding_image_batch`` delegates to a pluggable *view source*; ``MeshViewSource`` is the one that renders the
+object's mesh on the GPU (meshrenderer.py, the HIP rasteriser) in place of the reference's OpenGL context.  The training
+pairs come from the same rasteriser (``Renderer.render_training_views``): the images are this rasteriser's, not an OpenGL
+driver's, and parity with a driver is unpinned exactly as for the codebook views.  ``Dataset.batch``, the background images
+and the augmentation pipeline stay out of scope (imgaug and cv2 are not dependencies).
 """
 from __future__ import annotations
 
+import hashlib
 import os
 
 import numpy as np
@@ -160,6 +162,78 @@ class Dataset(object):
     @property
     def embedding_size(self):
         return len(self.viewsphere_for_embedding)
+
+    # ---- the training set (dataset.py:82-95, 219-306, 354-373) -------------------------------------------------------
+    @lazy_property
+    def noof_training_imgs(self):
+        return int(self._kw['noof_training_imgs'])
+
+    def get_training_images(self, dataset_path, args, batch=256):
+        """dataset.py:82-95: load <md5 of the [Dataset] and [Paths] items>.npz from dataset_path, or render the training set
+        and write it there (train_x, mask_x, train_y); returns the file's path."""
+        current_config_hash = hashlib.md5((str(args.items('Dataset') + args.items('Paths'))).encode('utf-8')).hexdigest()
+        current_file_name = os.path.join(dataset_path, current_config_hash + '.npz')
+        if os.path.exists(current_file_name):
+            training_data = np.load(current_file_name)
+            self.train_x = training_data['train_x'].astype(np.uint8)
+            self.mask_x = training_data['mask_x']
+            self.train_y = training_data['train_y'].astype(np.uint8)
+        else:
+            self.render_training_images(batch)
+            np.savez(current_file_name, train_x=self.train_x, mask_x=self.mask_x, train_y=self.train_y)
+        self.noof_obj_pixels = np.count_nonzero(self.mask_x == 0, axis=(1, 2))
+        print('loaded %s training images' % len(self.train_x))
+        return current_file_name
+
+    def render_training_images(self, batch=256):
+        """dataset.py:219-306 on the GPU: train_x uint8 [N,H,W,3] (random light, cut around a randomly shifted box), mask_x bool
+        [N,H,W] (its background), train_y uint8 [N,H,W,3] (default light, true box) as host arrays, `batch` pairs a call.
+        np.random is consumed in the reference's order (meshrenderer.draw_training_params), all of it before the first
+        launch.  Deviation: an image whose view covers no pixel raises ValueError naming it; the reference prints the same
+        hint and leaves the loop with the rest of its arrays uninitialised."""
+        from . import meshrenderer
+        src = MeshViewSource(self)                               # the cfg parsing and the C = 1 / non-square errors of the codebook views
+        n = self.noof_training_imgs
+        max_rel_offset = float(self._kw['max_rel_offset'])
+        Rs, lights, offsets = meshrenderer.draw_training_params(n, max_rel_offset, self._kw['model'])
+        self.train_x = np.empty((n,) + self.shape, dtype=np.uint8)
+        self.mask_x = np.empty((n,) + self.shape[:2], dtype=bool)
+        self.train_y = np.empty((n,) + self.shape, dtype=np.uint8)
+        batch = max(1, int(batch))
+        for a in range(0, n, batch):
+            e = min(a + batch, n)
+            x, m, y, _, visible = src.renderer.render_training_views(0, src.render_dims[0], src.render_dims[1], src.K, Rs[a:e], src.t, src.clip_near,
+                                                                     src.clip_far, src.pad_factor, src.crop, lights[a:e], offsets[a:e])
+            hidden = np.nonzero(visible.cpu().numpy() == 0)[0]
+            if len(hidden):
+                raise ValueError('Object in Rendering not visible (training image %d). Have you scaled the vertices to mm?' % (a + int(hidden[0])))
+            self.train_x[a:e] = x.cpu().numpy()
+            self.mask_x[a:e] = m.cpu().numpy()
+            self.train_y[a:e] = y.cpu().numpy()
+
+    def extract_square_patch(self, scene_img, bb_xywh, pad_factor, resize=(128, 128), interpolation='nearest', black_borders=False):
+        """dataset.py:354-373 on the host in NumPy, with cv2.resize(INTER_NEAREST) restated (OpenCV resize.cpp, resizeNN);
+        interpolation: 'nearest' or cv2.INTER_NEAREST's value 0, anything else raises NotImplementedError."""
+        if not (interpolation == 'nearest' or (not isinstance(interpolation, str) and interpolation == 0)):
+            raise NotImplementedError('extract_square_patch: only nearest-neighbour interpolation is implemented, got %r' % (interpolation,))
+        scene_img = np.asarray(scene_img)
+        x, y, w, h = np.array(bb_xywh).astype(np.int32)
+        size = int(np.maximum(h, w) * pad_factor)
+        left = int(np.maximum(x + w / 2 - size / 2, 0))
+        right = int(np.minimum(x + w / 2 + size / 2, scene_img.shape[1]))
+        top = int(np.maximum(y + h / 2 - size / 2, 0))
+        bottom = int(np.minimum(y + h / 2 + size / 2, scene_img.shape[0]))
+        scene_crop = scene_img[top:bottom, left:right].copy()
+        if black_borders:
+            scene_crop[:(y - top), :] = 0
+            scene_crop[(y + h - top):, :] = 0
+            scene_crop[:, :(x - left)] = 0
+            scene_crop[:, (x + w - left):] = 0
+        src_h, src_w = scene_crop.shape[:2]
+        dst_w, dst_h = int(resize[0]), int(resize[1])
+        cols = np.minimum(np.floor(np.arange(dst_w) * (1.0 / (float(dst_w) / src_w))).astype(np.int64), src_w - 1)
+        rows = np.minimum(np.floor(np.arange(dst_h) * (1.0 / (float(dst_h) / src_h))).astype(np.int64), src_h - 1)
+        return scene_crop[rows][:, cols]
 
     def render_embedding_image_batch(self, start, end):
         """(batch float64 in [0,1] or uint8, obj_bbs) for codebook rows [start,end)

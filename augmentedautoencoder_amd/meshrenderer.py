@@ -4,11 +4,14 @@
 computed and how exactly), plus the PLY reader the reference loads its models with.
 
 No OpenGL, EGL or pyassimp: the mesh is uploaded once (``aae_mesh_create``) and every call renders a batch of views
-in six launches; ``render_many`` / ``render_scenes`` draw several models into one frame (``aae_render_scenes``).  Parity with a real OpenGL driver is unpinned; the geometry is reproducible bit for bit against the
+in six launches; ``render_many`` / ``render_scenes`` draw several models into one frame (``aae_render_scenes``);
+``render_training_views`` renders training pairs (``aae_render_training_views``: random light and shifted box next to default
+light and true box, the geometry done once).  Parity with a real OpenGL driver is unpinned; the geometry is reproducible bit for bit against the
 float64 restatement of the tests."""
 from __future__ import annotations
 
 import ctypes
+import math
 import struct
 
 import numpy as np
@@ -155,6 +158,47 @@ def draw_light(random_light, phong, kind):
     return tuple(light), ambient, diffuse, specular
 
 
+def random_rotation_matrix(rand=None):
+    """pysixd_stuff/transform.py:1463-1503 (random_quaternion + quaternion_matrix): a uniform random rotation as a homogeneous
+    4x4 matrix from three uniforms in [0, 1), drawn with np.random.rand(3) when not given; the reference's float64 operations in
+    the reference's order, so the same seed gives the same bits."""
+    if rand is None:
+        rand = np.random.rand(3)
+    else:
+        assert len(rand) == 3
+    r1 = np.sqrt(1.0 - rand[0])
+    r2 = np.sqrt(rand[0])
+    pi2 = math.pi * 2.0
+    t1 = pi2 * rand[1]
+    t2 = pi2 * rand[2]
+    q = np.array([np.cos(t2) * r2, np.sin(t1) * r1, np.cos(t1) * r1, np.sin(t2) * r2], dtype=np.float64)
+    n = np.dot(q, q)
+    if n < np.finfo(float).eps * 4.0:
+        return np.identity(4)
+    q *= math.sqrt(2.0 / n)
+    q = np.outer(q, q)
+    return np.array([
+        [1.0 - q[2, 2] - q[3, 3], q[1, 2] - q[3, 0], q[1, 3] + q[2, 0], 0.0],
+        [q[1, 2] + q[3, 0], 1.0 - q[1, 1] - q[3, 3], q[2, 3] - q[1, 0], 0.0],
+        [q[1, 3] - q[2, 0], q[2, 3] + q[1, 0], 1.0 - q[1, 1] - q[2, 2], 0.0],
+        [0.0, 0.0, 0.0, 1.0]])
+
+
+def draw_training_params(n, max_rel_offset, kind, phong=None):
+    """The random numbers of n passes of the loop of dataset.py:238-285, drawn from np.random in the loop's order -- per image
+    rand(3) for the rotation, the light of the train_x render (draw_light(True, ...)), uniform(-m, m) for x, then for y -- as
+    (Rs float64 [n,3,3], lights float64 [n,6]: position, ambient, diffuse, specular, offsets float64 [n,2]).  The reference
+    multiplies the offsets by the box's width and height afterwards, so every draw can precede the rendering."""
+    Rs, lights, offsets = np.empty((n, 3, 3)), np.empty((n, 6)), np.empty((n, 2))
+    for i in range(n):
+        Rs[i] = random_rotation_matrix()[:3, :3]
+        light, a, d, s = draw_light(True, phong, kind)
+        lights[i] = light + (a, d, s)
+        offsets[i, 0] = np.random.uniform(-max_rel_offset, max_rel_offset)
+        offsets[i, 1] = np.random.uniform(-max_rel_offset, max_rel_offset)
+    return Rs, lights, offsets
+
+
 def render_params(W, H, K, t, near, far, pad_factor=1.0, light=DEFAULT_LIGHT, ambient=0.4, diffuse=0.8, specular=0.3):
     p = _lib.RenderParams()
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
@@ -235,10 +279,11 @@ class Renderer(object):
         return ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
 
     # ---- rendering ------------------------------------------------------------------
-    def render_batch(self, obj_id, W, H, K, Rs, ts, near, far, random_light=False, phong=None, workspace=None, return_tri=False):
+    def render_batch(self, obj_id, W, H, K, Rs, ts, near, far, random_light=False, phong=None, workspace=None, return_tri=False, light=None):
         """n views in one call: Rs [n,3,3], ts [n,3] or one [3] for all -> (bgr uint8 [n,H,W,3], depth float32 [n,H,W],
         obj_bbs int32 [n,4], visible int32 [n]) as device tensors, with return_tri=True also the index of the visible face
-        per pixel (int32 [n,H,W], -1 = background).  One light for the batch, as one render call has."""
+        per pixel (int32 [n,H,W], -1 = background).  One light for the batch, as one render call has: draw_light's, or the
+        explicit light = (position, ambient, diffuse, specular)."""
         import torch
         self._open()
         assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
@@ -250,7 +295,7 @@ class Renderer(object):
         td = None if t_arr.size == 3 else self._upload(t_arr, 3)
         if td is not None and td.shape[0] != n:
             raise ValueError('%d rotations, %d translations' % (n, td.shape[0]))
-        light, a, d, s = draw_light(random_light, phong, self.model)
+        light, a, d, s = draw_light(random_light, phong, self.model) if light is None else light
         p = render_params(W, H, K, t_arr if td is None else None, near, far, 1.0, light, a, d, s)
         with torch.cuda.device(self._device):
             bgr = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self._device)
@@ -295,6 +340,46 @@ class Renderer(object):
                 return crops, bbs, vis, list(ms)
             _lib.check(self.lib, self.lib.aae_render_embedding_views(*args), 'aae_render_embedding_views')
         return crops, bbs, vis
+
+    def render_training_views(self, obj_id, W, H, K, Rs, t, near, far, pad_factor, crop, lights, offsets, phong=None, workspace=None, timed=False):
+        """n passes of the loop of dataset.py:238-303 at one translation, the geometry of a pair rendered once: lights [n,6]
+        (position, ambient, diffuse, specular of the train_x render), offsets [n,2] (the shift of train_x's box in units of its
+        width and height) -> (train_x uint8 [n,crop,crop,3] BGR, mask_x bool [n,crop,crop], train_y uint8 [n,crop,crop,3],
+        obj_bbs int32 [n,4], visible int32 [n]) as device tensors; with timed=True also the milliseconds of the six launches.
+        train_y has the default light with phong's constants.  A view that covers no pixel has flag 0, zero crops and a mask
+        of all ones."""
+        import torch
+        self._open()
+        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
+        W, H, crop = int(W), int(H), int(crop)
+        mesh = self._meshes[obj_id]
+        Rd = self._upload(Rs, 9)
+        n = Rd.shape[0]
+        Ld = self._upload(lights, 6).to(torch.float32)
+        Od = self._upload(offsets, 2)
+        if Ld.shape[0] != n or Od.shape[0] != n:
+            raise ValueError('%d rotations, %d lights, %d offsets' % (n, Ld.shape[0], Od.shape[0]))
+        light, a, d, s = draw_light(False, phong, self.model)
+        p = render_params(W, H, K, t, near, far, pad_factor, light, a, d, s)
+        with torch.cuda.device(self._device):
+            train_x = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
+            train_y = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
+            mask_x = torch.empty((n, crop, crop), dtype=torch.uint8, device=self._device)
+            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
+            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
+            if workspace is not None:
+                ws_ptr, ws_bytes = workspace
+            else:
+                ws_ptr, ws_bytes = self._workspace(mesh, n, W, H, need=self.lib.aae_render_training_workspace_bytes(mesh, n, W, H))
+            args = (mesh, ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(Ld.data_ptr()), ctypes.c_void_p(Od.data_ptr()), n, ctypes.byref(p), crop,
+                    ctypes.c_void_p(train_x.data_ptr()), ctypes.c_void_p(mask_x.data_ptr()), ctypes.c_void_p(train_y.data_ptr()),
+                    ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
+            if timed:
+                ms = (ctypes.c_float * 6)()
+                _lib.check(self.lib, self.lib.aae_render_training_views_timed(*(args + (ms,))), 'aae_render_training_views_timed')
+                return train_x, mask_x.view(torch.bool), train_y, bbs, vis, list(ms)
+            _lib.check(self.lib, self.lib.aae_render_training_views(*args), 'aae_render_training_views')
+        return train_x, mask_x.view(torch.bool), train_y, bbs, vis
 
     def render(self, obj_id, W, H, K, R, t, near, far, random_light=False, phong=None):
         """meshrenderer_phong.py:101-168 / meshrenderer.py:84-137: (bgr uint8 [H,W,3], depth float32 [H,W]) on the host."""

@@ -393,6 +393,26 @@ int aae_render_frames(const aae_mesh* mesh, const double* Rs, const double* ts, 
                       void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* Training pairs: the loop of Dataset.render_training_images (auto_pose/ae/dataset.py:219-306) for n rotations at params->t, the
+ * geometry of a pair done once.  Rs device float64 [n,9]; lights device float32 [n,6] (position xyz in eye coordinates, ambient,
+ * diffuse, specular: the light train_x is drawn with); offsets device float64 [n,2] (u_x, u_y: train_x is cut around
+ * int32(obj_bb + [u_x w, u_y h, 0, 0]), dataset.py:282-285).  params: t, K, dims, near / far, pad_factor and the default light
+ * train_y is drawn with.  train_x / train_y device uint8 [n,crop,crop,3] BGR, mask_x device uint8 [n,crop,crop] (1 where the
+ * train_x sample is background), bbs_out device int32 [n,4] (the true box), visible_out device int32 [n] (0: no pixel covered;
+ * that view's crops are 0 and its mask all 1).  train_y is byte for byte aae_render_embedding_views of the same call, train_x
+ * what aae_render_frames with that view's light gives, cut around the shifted box.  The workspace
+ * (aae_render_training_workspace_bytes) may hold anything on entry; no allocation, no synchronisation, no copy from host
+ * memory: capturable into a graph.  n <= 65535. */
+size_t aae_render_training_workspace_bytes(const aae_mesh* mesh, int n_views, int W, int H);
+int aae_render_training_views(const aae_mesh* mesh, const double* Rs, const float* lights, const double* offsets, int n,
+                              const aae_render_params* params, int crop, void* train_x, void* mask_x, void* train_y, int32_t* bbs_out,
+                              int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream);
+/* the same call with the time of each of its six launches (init, vertex, clear, raster, bbox, crop) from events on `stream`;
+ * synchronises, so not for capture */
+int aae_render_training_views_timed(const aae_mesh* mesh, const double* Rs, const float* lights, const double* offsets, int n,
+                                    const aae_render_params* params, int crop, void* train_x, void* mask_x, void* train_y, int32_t* bbs_out,
+                                    int32_t* visible_out, void* workspace, size_t ws_bytes, void* stream, float* kernel_ms);
+
 /* Several meshes into one frame: Renderer.render_many (meshrenderer.py:140-194, meshrenderer_phong.py:170-224), which
  * PoseVisualizer.render_poses (visualization/render_pose.py) and the multi-object demos end in.  A draw is (mesh of a set, R, t,
  * scene); the draws of one scene share one depth buffer.  Per draw the fragments are those of aae_render_frames for that mesh and
