@@ -50,6 +50,39 @@ static int rfail(int code, const char* fmt, ...) {
             return aae_render::rfail(AAE_ERR_RUNTIME, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
 
+#define AAE_RENDER_OK(call) do { if (int rc__ = (call)) return rc__; } while (0)
+
+// the two model kinds of a kernel template: kernel<true> for AAE_MODEL_CAD, kernel<false> otherwise
+#define AAE_LAUNCH_KIND(cad, kernel, ...) do { if (cad) AAE_LAUNCH(kernel<true>, __VA_ARGS__); else AAE_LAUNCH(kernel<false>, __VA_ARGS__); } while (0)
+
+// The events of a timed call: seven marks around six launches, then one synchronise on the last.  An untimed call creates no
+// event and records nothing.  The destructor is the only place that destroys events, so no return between begin and finish leaks one.
+struct StageTimer {
+    hipEvent_t ev[7] = {};
+    int made = 0, stage = 0;
+    bool timed = false;
+
+    int begin(bool timed_) {
+        timed = timed_;
+        for (int i = 0; timed && i < 7; ++i, ++made) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
+        return AAE_OK;
+    }
+    int mark(hipStream_t stream) {
+        if (timed) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream));
+        return AAE_OK;
+    }
+    // after the last mark; kernel_ms: 6 floats when timed
+    int finish(float* kernel_ms) {
+        AAE_RENDER_TRY(hipGetLastError());
+        if (timed) {
+            AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
+            for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
+        }
+        return AAE_OK;
+    }
+    ~StageTimer() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); }
+};
+
 static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct WsLayout {
@@ -70,18 +103,36 @@ static WsLayout ws_layout(int V, int n, int W, int H, int n_vary = RC_VARY) {
 #define AAE_RENDER_MAX_DIM 4096
 #define AAE_RENDER_MAX_VIEWS 65535           /* the view is blockIdx.y */
 
-// the checks every batch-of-views call makes after its null checks, in this order; crop: nullptr when the call cuts no patches
-static int check_views(int n, const aae_render_params* p, const int* crop, const WsLayout& l, const void* ws, size_t ws_bytes, const char* who) {
-    if (n < 1 || n > AAE_RENDER_MAX_VIEWS) return rfail(AAE_ERR_UNSUPPORTED, "%s: %d views outside [1,%d] per call", who, n, AAE_RENDER_MAX_VIEWS);
+// frame size, K and the clip planes, in this order
+static int check_camera(const aae_render_params* p, const char* who) {
     if (p->W < 1 || p->H < 1 || p->W > AAE_RENDER_MAX_DIM || p->H > AAE_RENDER_MAX_DIM)
         return rfail(AAE_ERR_UNSUPPORTED, "%s: render dims %dx%d outside [1,%d]", who, p->W, p->H, AAE_RENDER_MAX_DIM);
     if (p->K[3] != 0.0 || p->K[6] != 0.0 || p->K[7] != 0.0)
         return rfail(AAE_ERR_INVALID, "%s: K[1,0], K[2,0] and K[2,1] must be 0", who);
     if (!(p->clip_near > 0.0) || !(p->clip_far > p->clip_near)) return rfail(AAE_ERR_INVALID, "%s: need 0 < near < far", who);
-    if (crop && (*crop < 1 || *crop > AAE_RENDER_MAX_DIM)) return rfail(AAE_ERR_UNSUPPORTED, "%s: crop size %d outside [1,%d]", who, *crop, AAE_RENDER_MAX_DIM);
-    if (ws_bytes < l.total) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    return AAE_OK;
+}
+
+static int check_workspace(const void* ws, size_t ws_bytes, size_t need, const char* who) {
+    if (ws_bytes < need) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
     if (((uintptr_t)ws & 255) != 0) return rfail(AAE_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
     return AAE_OK;
+}
+
+// the checks every batch-of-views call makes after its null checks, in this order; crop: nullptr when the call cuts no patches
+static int check_views(int n, const aae_render_params* p, const int* crop, const WsLayout& l, const void* ws, size_t ws_bytes, const char* who) {
+    if (n < 1 || n > AAE_RENDER_MAX_VIEWS) return rfail(AAE_ERR_UNSUPPORTED, "%s: %d views outside [1,%d] per call", who, n, AAE_RENDER_MAX_VIEWS);
+    AAE_RENDER_OK(check_camera(p, who));
+    if (crop && (*crop < 1 || *crop > AAE_RENDER_MAX_DIM)) return rfail(AAE_ERR_UNSUPPORTED, "%s: crop size %d outside [1,%d]", who, *crop, AAE_RENDER_MAX_DIM);
+    return check_workspace(ws, ws_bytes, l.total, who);
+}
+
+static void fill_camera_light(const aae_render_params* p, RcCamera* cam, RcLight* light) {
+    cam->K00 = p->K[0]; cam->K01 = p->K[1]; cam->K02 = p->K[2]; cam->K11 = p->K[4]; cam->K12 = p->K[5];
+    cam->near_ = p->clip_near; cam->far_ = p->clip_far;
+    cam->W = p->W; cam->H = p->H;
+    light->pos[0] = p->light[0]; light->pos[1] = p->light[1]; light->pos[2] = p->light[2];
+    light->ambient = p->ambient; light->diffuse = p->diffuse; light->specular = p->specular;
 }
 
 static RenderArgs render_args(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, const WsLayout& l, void* ws) {
@@ -91,11 +142,7 @@ static RenderArgs render_args(const aae_mesh* m, const double* Rs, const double*
     a.V = m->V; a.F = m->F;
     a.Rs = Rs; a.ts = ts;
     a.t[0] = p->t[0]; a.t[1] = p->t[1]; a.t[2] = p->t[2];
-    a.cam.K00 = p->K[0]; a.cam.K01 = p->K[1]; a.cam.K02 = p->K[2]; a.cam.K11 = p->K[4]; a.cam.K12 = p->K[5];
-    a.cam.near_ = p->clip_near; a.cam.far_ = p->clip_far;
-    a.cam.W = p->W; a.cam.H = p->H;
-    a.light.pos[0] = p->light[0]; a.light.pos[1] = p->light[1]; a.light.pos[2] = p->light[2];
-    a.light.ambient = p->ambient; a.light.diffuse = p->diffuse; a.light.specular = p->specular;
+    fill_camera_light(p, &a.cam, &a.light);
     a.n = n;
     a.rect = (int32_t*)(base + l.rect);
     a.vtx = (RcVertex*)(base + l.vtx);
@@ -104,106 +151,76 @@ static RenderArgs render_args(const aae_mesh* m, const double* Rs, const double*
     return a;
 }
 
+// The six launches of a batch of views of one mesh.  vertex(grid, block) launches the vertex form and final_stage(block) the last
+// kernel (crops, frames or training pairs); the four launches between and around them are the same for every call.
 // kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+template <class Vertex, class Final>
+static int views_run(const RenderArgs& a, int32_t* bbs_out, int32_t* visible_out, hipStream_t stream, float* kernel_ms, Vertex vertex,
+                     Final final_stage) {
+    StageTimer tm;
+    AAE_RENDER_OK(tm.begin(kernel_ms != nullptr));
+    const dim3 block(RENDER_BLOCK);
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH(render_init_rect, dim3((a.n + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
+    AAE_RENDER_OK(tm.mark(stream));
+    vertex(dim3((a.V + RENDER_BLOCK - 1) / RENDER_BLOCK, a.n), block);
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH(render_clear, dim3(RENDER_CLEAR_BLOCKS, a.n), block, 0, stream, a);
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH(render_raster, dim3((a.F + RENDER_BLOCK - 1) / RENDER_BLOCK, a.n), block, 0, stream, a);
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH(render_bbox, dim3(a.n), block, 0, stream, a, bbs_out, visible_out);
+    AAE_RENDER_OK(tm.mark(stream));
+    final_stage(block);
+    AAE_RENDER_OK(tm.mark(stream));
+    return tm.finish(kernel_ms);
+}
+
+// embedding crops (crops_out) or full frames (bgr_out, depth_out, tri_out)
 static int render_run(const aae_mesh* m, const double* Rs, const double* ts, int n, const aae_render_params* p, int crop,
                       void* crops_out, void* bgr_out, float* depth_out, int32_t* tri_out, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes,
                       void* stream_, float* kernel_ms, const char* who) {
     if (!m || !Rs || !p || !bbs_out || !visible_out || !ws) return rfail(AAE_ERR_INVALID, "%s: null argument", who);
     const WsLayout l = ws_layout(m->V, n, p->W, p->H);
-    if (int rc = check_views(n, p, crops_out ? &crop : nullptr, l, ws, ws_bytes, who)) return rc;
+    AAE_RENDER_OK(check_views(n, p, crops_out ? &crop : nullptr, l, ws, ws_bytes, who));
 
     hipStream_t stream = (hipStream_t)stream_;
     const RenderArgs a = render_args(m, Rs, ts, n, p, l, ws);
-
-    hipEvent_t ev[7] = {};
-    if (kernel_ms)
-        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
-    int stage = 0;
-#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
     const bool cad = m->model == AAE_MODEL_CAD;
-    const dim3 block(RENDER_BLOCK);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_init_rect, dim3((n + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    const dim3 vgrid((m->V + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
-    if (cad) AAE_LAUNCH(render_vertex<true>, vgrid, block, 0, stream, a);
-    else AAE_LAUNCH(render_vertex<false>, vgrid, block, 0, stream, a);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_clear, dim3(RENDER_CLEAR_BLOCKS, n), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_raster, dim3((m->F + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_bbox, dim3(n), block, 0, stream, a, bbs_out, visible_out);
-    AAE_RENDER_MARK();
-    if (crops_out) {
-        const dim3 cgrid((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
-        if (cad) AAE_LAUNCH(render_crop<true>, cgrid, block, 0, stream, a, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)crops_out);
-        else AAE_LAUNCH(render_crop<false>, cgrid, block, 0, stream, a, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)crops_out);
-    } else {
-        const dim3 fgrid((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
-        if (cad) AAE_LAUNCH(render_frame<true>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
-        else AAE_LAUNCH(render_frame<false>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, tri_out);
-    }
-    AAE_RENDER_MARK();
-#undef AAE_RENDER_MARK
-    AAE_RENDER_TRY(hipGetLastError());
-    if (kernel_ms) {
-        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
-        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
-        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
-    }
-    return AAE_OK;
+    return views_run(
+        a, bbs_out, visible_out, stream, kernel_ms,
+        [&](dim3 grid, dim3 block) { AAE_LAUNCH_KIND(cad, render_vertex, grid, block, 0, stream, a); },
+        [&](dim3 block) {
+            if (crops_out)
+                AAE_LAUNCH_KIND(cad, render_crop, dim3((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a, (const int32_t*)bbs_out,
+                                (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)crops_out);
+            else
+                AAE_LAUNCH_KIND(cad, render_frame, dim3((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a, (uint8_t*)bgr_out, depth_out,
+                                tri_out);
+        });
 }
 
-// a batch of training pairs: render_run's launches with the training forms of the vertex stage and the crop
-// kernel_ms: nullptr, or 6 floats (the timed variant: events around every launch, then a synchronise)
+// a batch of training pairs: the launches of a batch of views with the training forms of the vertex stage and the crop
 static int train_run(const aae_mesh* m, const double* Rs, const float* lights, const double* offsets, int n, const aae_render_params* p, int crop,
                      void* train_x, void* mask_x, void* train_y, int32_t* bbs_out, int32_t* visible_out, void* ws, size_t ws_bytes, void* stream_,
                      float* kernel_ms, const char* who) {
     if (!m || !Rs || !lights || !offsets || !p || !train_x || !mask_x || !train_y || !bbs_out || !visible_out || !ws)
         return rfail(AAE_ERR_INVALID, "%s: null argument", who);
     const WsLayout l = ws_layout(m->V, n, p->W, p->H, RC_VARY_TRAIN);
-    if (int rc = check_views(n, p, &crop, l, ws, ws_bytes, who)) return rc;
+    AAE_RENDER_OK(check_views(n, p, &crop, l, ws, ws_bytes, who));
 
     hipStream_t stream = (hipStream_t)stream_;
     const RenderArgs a = render_args(m, Rs, nullptr, n, p, l, ws);
     TrainArgs ta;
     ta.lights = lights; ta.offsets = offsets;
-
-    hipEvent_t ev[7] = {};
-    if (kernel_ms)
-        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
-    int stage = 0;
-#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
     const bool cad = m->model == AAE_MODEL_CAD;
-    const dim3 block(RENDER_BLOCK);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_init_rect, dim3((n + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    const dim3 vgrid((m->V + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
-    if (cad) AAE_LAUNCH(render_vertex_train<true>, vgrid, block, 0, stream, a, ta);
-    else AAE_LAUNCH(render_vertex_train<false>, vgrid, block, 0, stream, a, ta);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_clear, dim3(RENDER_CLEAR_BLOCKS, n), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_raster, dim3((m->F + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    AAE_LAUNCH(render_bbox, dim3(n), block, 0, stream, a, bbs_out, visible_out);
-    AAE_RENDER_MARK();
-    const dim3 cgrid((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n);
-    if (cad) AAE_LAUNCH(render_train_crop<true>, cgrid, block, 0, stream, a, ta, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop,
-                        (uint8_t*)train_x, (uint8_t*)mask_x, (uint8_t*)train_y);
-    else AAE_LAUNCH(render_train_crop<false>, cgrid, block, 0, stream, a, ta, (const int32_t*)bbs_out, (const int32_t*)visible_out, p->pad_factor, crop,
-                    (uint8_t*)train_x, (uint8_t*)mask_x, (uint8_t*)train_y);
-    AAE_RENDER_MARK();
-#undef AAE_RENDER_MARK
-    AAE_RENDER_TRY(hipGetLastError());
-    if (kernel_ms) {
-        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
-        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
-        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
-    }
-    return AAE_OK;
+    return views_run(
+        a, bbs_out, visible_out, stream, kernel_ms,
+        [&](dim3 grid, dim3 block) { AAE_LAUNCH_KIND(cad, render_vertex_train, grid, block, 0, stream, a, ta); },
+        [&](dim3 block) {
+            AAE_LAUNCH_KIND(cad, render_train_crop, dim3((crop * crop + RENDER_BLOCK - 1) / RENDER_BLOCK, n), block, 0, stream, a, ta, (const int32_t*)bbs_out,
+                            (const int32_t*)visible_out, p->pad_factor, crop, (uint8_t*)train_x, (uint8_t*)mask_x, (uint8_t*)train_y);
+        });
 }
 
 struct SceneLayout {
@@ -240,11 +257,7 @@ static int scene_run(const aae_mesh_set* set, const int32_t* obj_ids, const int3
         return rfail(AAE_ERR_UNSUPPORTED, "%s: %d scenes outside [1,%d] per call", who, n_scenes, AAE_SCENE_MAX_SCENES);
     if (!rc_scene_fits((uint64_t)n_draws, (uint64_t)set->Fmax))
         return rfail(AAE_ERR_UNSUPPORTED, "%s: %d draws of up to %d faces do not fit the 32-bit index of the visibility key", who, n_draws, set->Fmax);
-    if (p->W < 1 || p->H < 1 || p->W > AAE_RENDER_MAX_DIM || p->H > AAE_RENDER_MAX_DIM)
-        return rfail(AAE_ERR_UNSUPPORTED, "%s: render dims %dx%d outside [1,%d]", who, p->W, p->H, AAE_RENDER_MAX_DIM);
-    if (p->K[3] != 0.0 || p->K[6] != 0.0 || p->K[7] != 0.0)
-        return rfail(AAE_ERR_INVALID, "%s: K[1,0], K[2,0] and K[2,1] must be 0", who);
-    if (!(p->clip_near > 0.0) || !(p->clip_far > p->clip_near)) return rfail(AAE_ERR_INVALID, "%s: need 0 < near < far", who);
+    AAE_RENDER_OK(check_camera(p, who));
     SceneArgs a;
     memset(&a.draws, 0, sizeof(a.draws));
     for (int d = 0; d < n_draws; ++d) {
@@ -256,19 +269,14 @@ static int scene_run(const aae_mesh_set* set, const int32_t* obj_ids, const int3
         a.draws.scene[d] = (uint16_t)scene_ids[d];
     }
     const SceneLayout l = scene_layout(set->Vmax, set->Fmax, n_draws, n_scenes, p->W, p->H);
-    if (ws_bytes < l.total) return rfail(AAE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
-    if (((uintptr_t)ws & 255) != 0) return rfail(AAE_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+    AAE_RENDER_OK(check_workspace(ws, ws_bytes, l.total, who));
 
     hipStream_t stream = (hipStream_t)stream_;
     char* base = (char*)ws;
     a.meshes = set->table;
     a.Vmax = set->Vmax; a.Fmax = set->Fmax;
     a.Rs = Rs; a.ts = ts;
-    a.cam.K00 = p->K[0]; a.cam.K01 = p->K[1]; a.cam.K02 = p->K[2]; a.cam.K11 = p->K[4]; a.cam.K12 = p->K[5];
-    a.cam.near_ = p->clip_near; a.cam.far_ = p->clip_far;
-    a.cam.W = p->W; a.cam.H = p->H;
-    a.light.pos[0] = p->light[0]; a.light.pos[1] = p->light[1]; a.light.pos[2] = p->light[2];
-    a.light.ambient = p->ambient; a.light.diffuse = p->diffuse; a.light.specular = p->specular;
+    fill_camera_light(p, &a.cam, &a.light);
     a.n_draws = n_draws; a.n_scenes = n_scenes;
     a.rect = (int32_t*)(base + l.rect);
     a.bounds = (int32_t*)(base + l.bounds);
@@ -278,39 +286,26 @@ static int scene_run(const aae_mesh_set* set, const int32_t* obj_ids, const int3
     a.vary = (float*)(base + l.vary);
     a.keys = (unsigned long long*)(base + l.keys);
 
-    hipEvent_t ev[7] = {};
-    if (kernel_ms)
-        for (int i = 0; i < 7; ++i) AAE_RENDER_TRY(hipEventCreate(&ev[i]));
-    int stage = 0;
-#define AAE_RENDER_MARK() do { if (kernel_ms) AAE_RENDER_TRY(hipEventRecord(ev[stage++], stream)); } while (0)
+    StageTimer tm;
+    AAE_RENDER_OK(tm.begin(kernel_ms != nullptr));
     const bool cad = set->model == AAE_MODEL_CAD;
     const dim3 block(RENDER_BLOCK);
     const int n_init = n_draws > n_scenes ? n_draws : n_scenes;
-    AAE_RENDER_MARK();
+    AAE_RENDER_OK(tm.mark(stream));
     AAE_LAUNCH(scene_init, dim3((n_init + RENDER_BLOCK - 1) / RENDER_BLOCK), block, 0, stream, a);
-    AAE_RENDER_MARK();
-    const dim3 vgrid((set->Vmax + RENDER_BLOCK - 1) / RENDER_BLOCK, n_draws);
-    if (cad) AAE_LAUNCH(scene_vertex<true>, vgrid, block, 0, stream, a);
-    else AAE_LAUNCH(scene_vertex<false>, vgrid, block, 0, stream, a);
-    AAE_RENDER_MARK();
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH_KIND(cad, scene_vertex, dim3((set->Vmax + RENDER_BLOCK - 1) / RENDER_BLOCK, n_draws), block, 0, stream, a);
+    AAE_RENDER_OK(tm.mark(stream));
     AAE_LAUNCH(scene_clear, dim3(RENDER_CLEAR_BLOCKS, n_scenes), block, 0, stream, a);
-    AAE_RENDER_MARK();
+    AAE_RENDER_OK(tm.mark(stream));
     AAE_LAUNCH(scene_raster, dim3(a.raster_blocks, n_draws), block, 0, stream, a);
-    AAE_RENDER_MARK();
+    AAE_RENDER_OK(tm.mark(stream));
     AAE_LAUNCH(scene_bbox, dim3(n_draws), dim3(64), 0, stream, a, bbs_out, visible_out);
-    AAE_RENDER_MARK();
-    const dim3 fgrid((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n_scenes);
-    if (cad) AAE_LAUNCH(scene_frame<true>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, draw_out, tri_out);
-    else AAE_LAUNCH(scene_frame<false>, fgrid, block, 0, stream, a, (uint8_t*)bgr_out, depth_out, draw_out, tri_out);
-    AAE_RENDER_MARK();
-#undef AAE_RENDER_MARK
-    AAE_RENDER_TRY(hipGetLastError());
-    if (kernel_ms) {
-        AAE_RENDER_TRY(hipEventSynchronize(ev[6]));
-        for (int i = 0; i < 6; ++i) AAE_RENDER_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
-        for (int i = 0; i < 7; ++i) (void)hipEventDestroy(ev[i]);
-    }
-    return AAE_OK;
+    AAE_RENDER_OK(tm.mark(stream));
+    AAE_LAUNCH_KIND(cad, scene_frame, dim3((p->W * p->H + RENDER_BLOCK - 1) / RENDER_BLOCK, n_scenes), block, 0, stream, a, (uint8_t*)bgr_out, depth_out,
+                    draw_out, tri_out);
+    AAE_RENDER_OK(tm.mark(stream));
+    return tm.finish(kernel_ms);
 }
 
 }  // namespace aae_render

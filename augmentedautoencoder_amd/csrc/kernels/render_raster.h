@@ -12,6 +12,10 @@
 //                        visibility buffer (the colour frame is never materialised)
 //   render_frame         full frames: BGR + fp32 depth (+ the index of the visible face)
 //
+// The bodies of the stages are __device__ functions of this file (rect_reset, vertex_stage, clear_rect, raster_stage,
+// block_bounds, key_at, shade_of): the scene kernels (render_scene.h) and the training forms (render_train.h) are other
+// iteration spaces and reductions around the same bodies.
+//
 // Visibility is a 64-bit atomicMin per fragment on global memory (a vector atomic); everything else is plain stores.
 #pragma once
 
@@ -41,11 +45,14 @@ struct RenderArgs {
     unsigned long long* keys;        // [n,H,W]
 };
 
+// the empty rectangle of a view (scene): every usable vertex shrinks x0, y0 and grows x1, y1
+__device__ inline void rect_reset(int32_t* r) {
+    r[0] = INT32_MAX; r[1] = INT32_MAX; r[2] = INT32_MIN; r[3] = INT32_MIN;
+}
+
 __global__ void __launch_bounds__(RENDER_BLOCK) render_init_rect(RenderArgs a) {
     const int v = blockIdx.x * RENDER_BLOCK + threadIdx.x;
-    if (v >= a.n) return;
-    int32_t* r = a.rect + (size_t)v * 4;
-    r[0] = INT32_MAX; r[1] = INT32_MAX; r[2] = INT32_MIN; r[3] = INT32_MIN;
+    if (v < a.n) rect_reset(a.rect + (size_t)v * 4);
 }
 
 __device__ inline int wave_min(int v) {
@@ -60,47 +67,87 @@ __device__ inline int wave_max(int v) {
     return v;
 }
 
+__device__ inline void wave_bounds(RcBounds* b) {
+    b->x0 = wave_min(b->x0); b->y0 = wave_min(b->y0); b->x1 = wave_max(b->x1); b->y1 = wave_max(b->y1);
+}
+
+// bounds over the block; the result is valid in thread 0.  Every thread of the block must call it.
+__device__ inline void block_bounds(RcBounds* b) {
+    __shared__ int red[4][RENDER_BLOCK / 64];
+    wave_bounds(b);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wv] = b->x0; red[1][wv] = b->y0; red[2][wv] = b->x1; red[3][wv] = b->y1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < RENDER_BLOCK / 64; ++k) {
+            b->x0 = min(b->x0, red[0][k]); b->y0 = min(b->y0, red[1][k]); b->x1 = max(b->x1, red[2][k]); b->y1 = max(b->y1, red[3][k]);
+        }
+    }
+}
+
+// The vertex stage of one vertex: vertex i of the mesh under (R, t) -> vtx[slot], its NV varyings -> vary_out[slot * NV ...]; returns
+// the pixels the vertex may touch, clamped to the frame (empty for a vertex no triangle may use).  more(Rr, t, p, vary) runs between
+// rc_vertex and the stores: the training form fills its varyings beyond RC_VARY there.  The kernels around it differ in how they
+// reduce the bounds.  (The slot's addresses are formed after rc_vertex: formed by the caller, the training form takes other registers.)
+template <bool CAD, int NV, class More>
+__device__ inline RcBounds vertex_stage(const double* R, const double* t, const RcCamera& cam, const RcLight& light, const float* verts,
+                                        const float* normals, int i, size_t slot, RcVertex* vtx, float* vary_out, More more) {
+    double Rr[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rr[k] = R[k];
+    const float p[3] = {verts[(size_t)i * 3], verts[(size_t)i * 3 + 1], verts[(size_t)i * 3 + 2]};
+    const float nr[3] = {normals[(size_t)i * 3], normals[(size_t)i * 3 + 1], normals[(size_t)i * 3 + 2]};
+    RcVertex out;
+    float vary[NV];
+    rc_vertex<CAD>(Rr, t, cam, light, p, nr, &out, vary);
+    more(Rr, t, p, vary);
+    vtx[slot] = out;
+    float* vd = vary_out + slot * NV;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) vd[k] = vary[k];
+    RcBounds b;
+    rc_bounds_empty(&b);
+    if (out.x != RC_INVALID) {
+        b.x0 = rc_clampi(rc_pixel_lo(out.x), 0, cam.W - 1);
+        b.x1 = rc_clampi(rc_pixel_hi(out.x), 0, cam.W - 1);
+        b.y0 = rc_clampi(rc_pixel_lo(out.y), 0, cam.H - 1);
+        b.y1 = rc_clampi(rc_pixel_hi(out.y), 0, cam.H - 1);
+    }
+    return b;
+}
+
+// the view's rectangle from the bounds of a block's vertices: one integer min / max atomic per wave and word
+__device__ inline void view_rect_add(const RenderArgs& a, int view, RcBounds b) {
+    wave_bounds(&b);
+    if ((threadIdx.x & 63) == 0 && b.x0 != INT32_MAX) {
+        int32_t* r = a.rect + (size_t)view * 4;
+        atomicMin(r + 0, b.x0);
+        atomicMin(r + 1, b.y0);
+        atomicMax(r + 2, b.x1);
+        atomicMax(r + 3, b.y1);
+    }
+}
+
 template <bool CAD>
 __global__ void __launch_bounds__(RENDER_BLOCK) render_vertex(RenderArgs a) {
     const int view = blockIdx.y;
     const int i = blockIdx.x * RENDER_BLOCK + threadIdx.x;
-    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    RcBounds b;
+    rc_bounds_empty(&b);
     if (i < a.V) {
-        const double* R = a.Rs + (size_t)view * 9;
         double t[3];
         if (a.ts) {
             t[0] = a.ts[(size_t)view * 3]; t[1] = a.ts[(size_t)view * 3 + 1]; t[2] = a.ts[(size_t)view * 3 + 2];
         } else {
             t[0] = a.t[0]; t[1] = a.t[1]; t[2] = a.t[2];
         }
-        double Rr[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rr[k] = R[k];
-        const float p[3] = {a.verts[(size_t)i * 3], a.verts[(size_t)i * 3 + 1], a.verts[(size_t)i * 3 + 2]};
-        const float nr[3] = {a.normals[(size_t)i * 3], a.normals[(size_t)i * 3 + 1], a.normals[(size_t)i * 3 + 2]};
-        RcVertex out;
-        float vary[RC_VARY];
-        rc_vertex<CAD>(Rr, t, a.cam, a.light, p, nr, &out, vary);
-        const size_t slot = (size_t)view * a.V + i;
-        a.vtx[slot] = out;
-        float* vd = a.vary + slot * RC_VARY;
-#pragma unroll
-        for (int k = 0; k < RC_VARY; ++k) vd[k] = vary[k];
-        if (out.x != RC_INVALID) {
-            x0 = rc_clampi(rc_pixel_lo(out.x), 0, a.cam.W - 1);
-            x1 = rc_clampi(rc_pixel_hi(out.x), 0, a.cam.W - 1);
-            y0 = rc_clampi(rc_pixel_lo(out.y), 0, a.cam.H - 1);
-            y1 = rc_clampi(rc_pixel_hi(out.y), 0, a.cam.H - 1);
-        }
+        b = vertex_stage<CAD, RC_VARY>(a.Rs + (size_t)view * 9, t, a.cam, a.light, a.verts, a.normals, i, (size_t)view * a.V + i, a.vtx, a.vary,
+                                       [](const double*, const double*, const float*, float*) {});
     }
-    x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1);
-    if ((threadIdx.x & 63) == 0 && x0 != INT32_MAX) {
-        int32_t* r = a.rect + (size_t)view * 4;
-        atomicMin(r + 0, x0);
-        atomicMin(r + 1, y0);
-        atomicMax(r + 2, x1);
-        atomicMax(r + 3, y1);
-    }
+    view_rect_add(a, view, b);
 }
 
 // the view's rectangle, or an empty one (w == 0) when no usable vertex set it
@@ -117,16 +164,20 @@ __device__ inline void load_rect(const RenderArgs& a, int view, int* x0, int* y0
     rect_of(a.rect + (size_t)view * 4, a.cam.W, a.cam.H, x0, y0, w, h);
 }
 
-__global__ void __launch_bounds__(RENDER_BLOCK) render_clear(RenderArgs a) {
-    const int view = blockIdx.y;
+// keys of the rectangle r of one key plane := background; the blocks of grid.x stride over the rectangle
+__device__ inline void clear_rect(const int32_t* r, unsigned long long* keys, int W, int H) {
     int x0, y0, w, h;
-    load_rect(a, view, &x0, &y0, &w, &h);
-    unsigned long long* keys = a.keys + (size_t)view * a.cam.W * a.cam.H;
+    rect_of(r, W, H, &x0, &y0, &w, &h);
     const int total = w * h;
     for (int i = blockIdx.x * RENDER_BLOCK + threadIdx.x; i < total; i += gridDim.x * RENDER_BLOCK) {
         const int y = y0 + i / w, x = x0 + i % w;
-        keys[(size_t)y * a.cam.W + x] = RC_BACKGROUND;
+        keys[(size_t)y * W + x] = RC_BACKGROUND;
     }
+}
+
+__global__ void __launch_bounds__(RENDER_BLOCK) render_clear(RenderArgs a) {
+    const int view = blockIdx.y;
+    clear_rect(a.rect + (size_t)view * 4, a.keys + (size_t)view * a.cam.W * a.cam.H, a.cam.W, a.cam.H);
 }
 
 // triangle `tri` of a face list, from the snapped vertices vv of its view (scenes: of its draw)
@@ -134,10 +185,6 @@ __device__ inline void tri_of(const int32_t* faces, const RcVertex* vv, int tri,
     const int32_t* f = faces + (size_t)tri * 3;
     const RcVertex v0 = vv[f[0]], v1 = vv[f[1]], v2 = vv[f[2]];
     rc_tri_setup(v0, v1, v2, W, H, T);
-}
-
-__device__ inline void load_tri(const RenderArgs& a, int view, int tri, RcTri* T) {
-    tri_of(a.faces, a.vtx + (size_t)view * a.V, tri, a.cam.W, a.cam.H, T);
 }
 
 // true when the pixel holds a fragment of the triangle (covered, not beyond the far plane), whether or not it is visible
@@ -151,21 +198,26 @@ __device__ inline bool raster_pixel(const RcTri& T, int x, int y, double far_, u
     return false;
 }
 
-__global__ void __launch_bounds__(RENDER_BLOCK) render_raster(RenderArgs a) {
-    const int view = blockIdx.y;
+// The raster stage of thread blockIdx.x * RENDER_BLOCK + threadIdx.x: triangle `tri` of the F faces, from the snapped vertices vv,
+// into the key plane `keys` with index base + tri.  BOUNDS: *b grows by the pixels the thread's fragments fell on.
+template <bool BOUNDS>
+__device__ inline void raster_stage(const int32_t* faces, int F, const RcVertex* vv, unsigned base, unsigned long long* keys, const RcCamera& cam,
+                                    RcBounds* b) {
     const int tri = blockIdx.x * RENDER_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    unsigned long long* keys = a.keys + (size_t)view * a.cam.W * a.cam.H;
     RcTri T;
     T.ok = 0;
     T.px0 = T.py0 = 0;
     T.px1 = T.py1 = -1;
-    if (tri < a.F) load_tri(a, view, tri, &T);
+    if (tri < F) tri_of(faces, vv, tri, cam.W, cam.H, &T);
     const int bw = T.px1 - T.px0 + 1, bh = T.py1 - T.py0 + 1;
     const bool large = T.ok && (long long)bw * bh > RENDER_WAVE_BOX;
     if (T.ok && !large) {
         for (int y = T.py0; y <= T.py1; ++y)
-            for (int x = T.px0; x <= T.px1; ++x) raster_pixel(T, x, y, a.cam.far_, (unsigned)tri, keys, a.cam.W);
+            for (int x = T.px0; x <= T.px1; ++x) {
+                const bool hit = raster_pixel(T, x, y, cam.far_, base + (unsigned)tri, keys, cam.W);
+                if constexpr (BOUNDS) if (hit) rc_bounds_add(b, x, y);
+            }
     }
     // the wave takes its large triangles one after the other, lanes striding over the pixel box
     unsigned long long todo = __ballot(large);
@@ -174,57 +226,47 @@ __global__ void __launch_bounds__(RENDER_BLOCK) render_raster(RenderArgs a) {
         todo &= todo - 1;
         const int wtri = __shfl(tri, src);
         RcTri S;
-        load_tri(a, view, wtri, &S);
+        tri_of(faces, vv, wtri, cam.W, cam.H, &S);
         const int sw = S.px1 - S.px0 + 1;
         const long long total = (long long)sw * (S.py1 - S.py0 + 1);
         for (long long i = lane; i < total; i += 64) {
             const int y = S.py0 + (int)(i / sw), x = S.px0 + (int)(i % sw);
-            raster_pixel(S, x, y, a.cam.far_, (unsigned)wtri, keys, a.cam.W);
+            const bool hit = raster_pixel(S, x, y, cam.far_, base + (unsigned)wtri, keys, cam.W);
+            if constexpr (BOUNDS) if (hit) rc_bounds_add(b, x, y);
         }
     }
+}
+
+__global__ void __launch_bounds__(RENDER_BLOCK) render_raster(RenderArgs a) {
+    const int view = blockIdx.y;
+    raster_stage<false>(a.faces, a.F, a.vtx + (size_t)view * a.V, 0u, a.keys + (size_t)view * a.cam.W * a.cam.H, a.cam, nullptr);
 }
 
 // calc_2d_bbox over the covered pixels of the view's rectangle; visible[view] = 0 when nothing is covered (bb := 0)
 __global__ void __launch_bounds__(RENDER_BLOCK) render_bbox(RenderArgs a, int32_t* bbs, int32_t* visible) {
-    __shared__ int red[4][RENDER_BLOCK / 64];
     const int view = blockIdx.x;
     int x0, y0, w, h;
     load_rect(a, view, &x0, &y0, &w, &h);
     const unsigned long long* keys = a.keys + (size_t)view * a.cam.W * a.cam.H;
-    int mnx = INT32_MAX, mny = INT32_MAX, mxx = INT32_MIN, mxy = INT32_MIN;
+    RcBounds b;
+    rc_bounds_empty(&b);
     const int total = w * h;
     for (int i = threadIdx.x; i < total; i += RENDER_BLOCK) {
         const int y = y0 + i / w, x = x0 + i % w;
-        if (keys[(size_t)y * a.cam.W + x] != RC_BACKGROUND) {
-            mnx = min(mnx, x); mny = min(mny, y); mxx = max(mxx, x); mxy = max(mxy, y);
-        }
+        if (keys[(size_t)y * a.cam.W + x] != RC_BACKGROUND) rc_bounds_add(&b, x, y);
     }
-    mnx = wave_min(mnx); mny = wave_min(mny); mxx = wave_max(mxx); mxy = wave_max(mxy);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wv] = mnx; red[1][wv] = mny; red[2][wv] = mxx; red[3][wv] = mxy;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < RENDER_BLOCK / 64; ++k) {
-            mnx = min(mnx, red[0][k]); mny = min(mny, red[1][k]); mxx = max(mxx, red[2][k]); mxy = max(mxy, red[3][k]);
-        }
-        int32_t* bb = bbs + (size_t)view * 4;
-        if (mnx == INT32_MAX) {
-            bb[0] = bb[1] = bb[2] = bb[3] = 0;
-            visible[view] = 0;
-        } else {
-            rc_bbox(mnx, mny, mxx, mxy, a.cam.W, a.cam.H, bb);
-            visible[view] = 1;
-        }
-    }
+    block_bounds(&b);
+    if (threadIdx.x == 0) rc_bounds_box(b, a.cam.W, a.cam.H, bbs + (size_t)view * 4, visible + view);
 }
 
-// key of frame pixel (x, y) of a view: background outside the view's rectangle (never cleared there, never read)
-__device__ inline unsigned long long key_at(const RenderArgs& a, int view, int x, int y, int rx0, int ry0, int rw, int rh) {
+// the key *k of pixel (x, y) of a key plane with rectangle (rx0, ry0, rw, rh): background outside it (never cleared there, never read)
+__device__ inline unsigned long long key_at(const unsigned long long* k, int x, int y, int rx0, int ry0, int rw, int rh) {
     if (x < rx0 || y < ry0 || x >= rx0 + rw || y >= ry0 + rh) return RC_BACKGROUND;
-    return a.keys[((size_t)view * a.cam.H + y) * a.cam.W + x];
+    return *k;
+}
+
+__device__ inline unsigned long long key_at(const RenderArgs& a, int view, int x, int y, int rx0, int ry0, int rw, int rh) {
+    return key_at(a.keys + ((size_t)view * a.cam.H + y) * a.cam.W + x, x, y, rx0, ry0, rw, rh);
 }
 
 // colour of the fragment of triangle `tri` at (x, y): vv / vb are the snapped vertices and varyings of its view (draw)

@@ -63,29 +63,9 @@ __device__ inline void shared_max(int32_t* p, int v) {
     if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
 }
 
-// (min, min, max, max) of four ints over the block; the result is valid in thread 0.  Every thread of the block must call it.
-__device__ inline void block_bounds(int* x0, int* y0, int* x1, int* y1) {
-    __shared__ int red[4][RENDER_BLOCK / 64];
-    *x0 = wave_min(*x0); *y0 = wave_min(*y0); *x1 = wave_max(*x1); *y1 = wave_max(*y1);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wv] = *x0; red[1][wv] = *y0; red[2][wv] = *x1; red[3][wv] = *y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < RENDER_BLOCK / 64; ++k) {
-            *x0 = min(*x0, red[0][k]); *y0 = min(*y0, red[1][k]); *x1 = max(*x1, red[2][k]); *y1 = max(*y1, red[3][k]);
-        }
-    }
-}
-
 __global__ void __launch_bounds__(RENDER_BLOCK) scene_init(SceneArgs a) {
     const int i = blockIdx.x * RENDER_BLOCK + threadIdx.x;
-    if (i < a.n_scenes) {
-        int32_t* r = a.rect + (size_t)i * 4;
-        r[0] = INT32_MAX; r[1] = INT32_MAX; r[2] = INT32_MIN; r[3] = INT32_MIN;
-    }
+    if (i < a.n_scenes) rect_reset(a.rect + (size_t)i * 4);
     if (i < a.n_draws) a.draw_obj[i] = a.draws.obj[i];
 }
 
@@ -94,95 +74,41 @@ __global__ void __launch_bounds__(RENDER_BLOCK) scene_vertex(SceneArgs a) {
     const int draw = blockIdx.y;
     const int i = blockIdx.x * RENDER_BLOCK + threadIdx.x;
     const SceneMesh m = a.meshes[a.draws.obj[draw]];
-    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    RcBounds b;
+    rc_bounds_empty(&b);
     if (i < m.V) {
-        const double* R = a.Rs + (size_t)draw * 9;
         const double t[3] = {a.ts[(size_t)draw * 3], a.ts[(size_t)draw * 3 + 1], a.ts[(size_t)draw * 3 + 2]};
-        double Rr[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rr[k] = R[k];
-        const float p[3] = {m.verts[(size_t)i * 3], m.verts[(size_t)i * 3 + 1], m.verts[(size_t)i * 3 + 2]};
-        const float nr[3] = {m.normals[(size_t)i * 3], m.normals[(size_t)i * 3 + 1], m.normals[(size_t)i * 3 + 2]};
-        RcVertex out;
-        float vary[RC_VARY];
-        rc_vertex<CAD>(Rr, t, a.cam, a.light, p, nr, &out, vary);
         const size_t slot = (size_t)draw * a.Vmax + i;
-        a.vtx[slot] = out;
-        float* vd = a.vary + slot * RC_VARY;
-#pragma unroll
-        for (int k = 0; k < RC_VARY; ++k) vd[k] = vary[k];
-        if (out.x != RC_INVALID) {
-            x0 = rc_clampi(rc_pixel_lo(out.x), 0, a.cam.W - 1);
-            x1 = rc_clampi(rc_pixel_hi(out.x), 0, a.cam.W - 1);
-            y0 = rc_clampi(rc_pixel_lo(out.y), 0, a.cam.H - 1);
-            y1 = rc_clampi(rc_pixel_hi(out.y), 0, a.cam.H - 1);
-        }
+        b = vertex_stage<CAD, RC_VARY>(a.Rs + (size_t)draw * 9, t, a.cam, a.light, m.verts, m.normals, i, slot, a.vtx, a.vary,
+                                       [](const double*, const double*, const float*, float*) {});
     }
-    block_bounds(&x0, &y0, &x1, &y1);
-    if (threadIdx.x == 0 && x0 != INT32_MAX) {
+    block_bounds(&b);
+    if (threadIdx.x == 0 && b.x0 != INT32_MAX) {
         int32_t* r = a.rect + (size_t)a.draws.scene[draw] * 4;
-        shared_min(r + 0, x0);
-        shared_min(r + 1, y0);
-        shared_max(r + 2, x1);
-        shared_max(r + 3, y1);
+        shared_min(r + 0, b.x0);
+        shared_min(r + 1, b.y0);
+        shared_max(r + 2, b.x1);
+        shared_max(r + 3, b.y1);
     }
 }
 
 __global__ void __launch_bounds__(RENDER_BLOCK) scene_clear(SceneArgs a) {
     const int scene = blockIdx.y;
-    int x0, y0, w, h;
-    rect_of(a.rect + (size_t)scene * 4, a.cam.W, a.cam.H, &x0, &y0, &w, &h);
-    unsigned long long* keys = a.keys + (size_t)scene * a.cam.W * a.cam.H;
-    const int total = w * h;
-    for (int i = blockIdx.x * RENDER_BLOCK + threadIdx.x; i < total; i += gridDim.x * RENDER_BLOCK) {
-        const int y = y0 + i / w, x = x0 + i % w;
-        keys[(size_t)y * a.cam.W + x] = RC_BACKGROUND;
-    }
+    clear_rect(a.rect + (size_t)scene * 4, a.keys + (size_t)scene * a.cam.W * a.cam.H, a.cam.W, a.cam.H);
 }
 
 __global__ void __launch_bounds__(RENDER_BLOCK) scene_raster(SceneArgs a) {
     const int draw = blockIdx.y;
-    const int tri = blockIdx.x * RENDER_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const SceneMesh m = a.meshes[a.draws.obj[draw]];
-    unsigned long long* keys = a.keys + (size_t)a.draws.scene[draw] * a.cam.W * a.cam.H;
-    const RcVertex* vv = a.vtx + (size_t)draw * a.Vmax;
-    const unsigned base = rc_scene_index((unsigned)draw, (unsigned)a.Fmax, 0u);
     RcBounds b;
     rc_bounds_empty(&b);
-    RcTri T;
-    T.ok = 0;
-    T.px0 = T.py0 = 0;
-    T.px1 = T.py1 = -1;
-    if (tri < m.F) tri_of(m.faces, vv, tri, a.cam.W, a.cam.H, &T);
-    const int bw = T.px1 - T.px0 + 1, bh = T.py1 - T.py0 + 1;
-    const bool large = T.ok && (long long)bw * bh > RENDER_WAVE_BOX;
-    if (T.ok && !large) {
-        for (int y = T.py0; y <= T.py1; ++y)
-            for (int x = T.px0; x <= T.px1; ++x)
-                if (raster_pixel(T, x, y, a.cam.far_, base + (unsigned)tri, keys, a.cam.W)) rc_bounds_add(&b, x, y);
-    }
-    // the wave takes its large triangles one after the other, lanes striding over the pixel box
-    unsigned long long todo = __ballot(large);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int wtri = __shfl(tri, src);
-        RcTri S;
-        tri_of(m.faces, vv, wtri, a.cam.W, a.cam.H, &S);
-        const int sw = S.px1 - S.px0 + 1;
-        const long long total = (long long)sw * (S.py1 - S.py0 + 1);
-        for (long long i = lane; i < total; i += 64) {
-            const int y = S.py0 + (int)(i / sw), x = S.px0 + (int)(i % sw);
-            if (raster_pixel(S, x, y, a.cam.far_, base + (unsigned)wtri, keys, a.cam.W)) rc_bounds_add(&b, x, y);
-        }
-    }
+    raster_stage<true>(m.faces, m.F, a.vtx + (size_t)draw * a.Vmax, rc_scene_index((unsigned)draw, (unsigned)a.Fmax, 0u),
+                       a.keys + (size_t)a.draws.scene[draw] * a.cam.W * a.cam.H, a.cam, &b);
     // the block's share of the draw's bounds: written by every block, empty or not, so the slot needs no initialisation
-    int x0 = b.x0, y0 = b.y0, x1 = b.x1, y1 = b.y1;
-    block_bounds(&x0, &y0, &x1, &y1);
+    block_bounds(&b);
     if (threadIdx.x == 0) {
         int32_t* d = a.bounds + ((size_t)draw * a.raster_blocks + blockIdx.x) * 4;
-        d[0] = x0; d[1] = y0; d[2] = x1; d[3] = y1;
+        d[0] = b.x0; d[1] = b.y0; d[2] = b.x1; d[3] = b.y1;
     }
 }
 
@@ -195,7 +121,7 @@ __global__ void __launch_bounds__(64) scene_bbox(SceneArgs a, int32_t* bbs, int3
     for (int k = threadIdx.x; k < a.raster_blocks; k += 64) {
         b.x0 = min(b.x0, d[k * 4]); b.y0 = min(b.y0, d[k * 4 + 1]); b.x1 = max(b.x1, d[k * 4 + 2]); b.y1 = max(b.y1, d[k * 4 + 3]);
     }
-    b.x0 = wave_min(b.x0); b.y0 = wave_min(b.y0); b.x1 = wave_max(b.x1); b.y1 = wave_max(b.y1);
+    wave_bounds(&b);
     if (threadIdx.x == 0) rc_bounds_box(b, a.cam.W, a.cam.H, bbs + (size_t)draw * 4, visible + draw);
 }
 
@@ -208,8 +134,7 @@ __global__ void __launch_bounds__(RENDER_BLOCK) scene_frame(SceneArgs a, uint8_t
     int rx0, ry0, rw, rh;
     rect_of(a.rect + (size_t)scene * 4, a.cam.W, a.cam.H, &rx0, &ry0, &rw, &rh);
     const size_t p = (size_t)scene * a.cam.W * a.cam.H + o;
-    // background outside the scene's rectangle (never cleared there, never read)
-    const unsigned long long key = (x < rx0 || y < ry0 || x >= rx0 + rw || y >= ry0 + rh) ? RC_BACKGROUND : a.keys[p];
+    const unsigned long long key = key_at(a.keys + p, x, y, rx0, ry0, rw, rh);
     int32_t draw, tri;
     rc_scene_decode(key, (uint32_t)a.Fmax, &draw, &tri);
     uint8_t bgr[3] = {0, 0, 0};

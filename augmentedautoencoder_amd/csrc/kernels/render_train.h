@@ -30,44 +30,22 @@ __device__ inline RcLight light_of(const float* lights, int view) {
     return out;
 }
 
-// a.vary holds RC_VARY_TRAIN floats per (view, vertex); a.ts is not read (one translation a call)
+// a.vary holds RC_VARY_TRAIN floats per (view, vertex); a.ts is null (one translation a call)
 template <bool CAD>
 __global__ void __launch_bounds__(RENDER_BLOCK) render_vertex_train(RenderArgs a, TrainArgs ta) {
     const int view = blockIdx.y;
     const int i = blockIdx.x * RENDER_BLOCK + threadIdx.x;
-    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    RcBounds b;
+    rc_bounds_empty(&b);
     if (i < a.V) {
-        const double* R = a.Rs + (size_t)view * 9;
         const double t[3] = {a.t[0], a.t[1], a.t[2]};
-        double Rr[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rr[k] = R[k];
-        const float p[3] = {a.verts[(size_t)i * 3], a.verts[(size_t)i * 3 + 1], a.verts[(size_t)i * 3 + 2]};
-        const float nr[3] = {a.normals[(size_t)i * 3], a.normals[(size_t)i * 3 + 1], a.normals[(size_t)i * 3 + 2]};
-        RcVertex out;
-        float vary[RC_VARY_TRAIN];
-        rc_vertex<CAD>(Rr, t, a.cam, a.light, p, nr, &out, vary);
-        rc_light_dir<CAD>(Rr, t, light_of(ta.lights, view), p, vary + RC_VARY);
         const size_t slot = (size_t)view * a.V + i;
-        a.vtx[slot] = out;
-        float* vd = a.vary + slot * RC_VARY_TRAIN;
-#pragma unroll
-        for (int k = 0; k < RC_VARY_TRAIN; ++k) vd[k] = vary[k];
-        if (out.x != RC_INVALID) {
-            x0 = rc_clampi(rc_pixel_lo(out.x), 0, a.cam.W - 1);
-            x1 = rc_clampi(rc_pixel_hi(out.x), 0, a.cam.W - 1);
-            y0 = rc_clampi(rc_pixel_lo(out.y), 0, a.cam.H - 1);
-            y1 = rc_clampi(rc_pixel_hi(out.y), 0, a.cam.H - 1);
-        }
+        b = vertex_stage<CAD, RC_VARY_TRAIN>(a.Rs + (size_t)view * 9, t, a.cam, a.light, a.verts, a.normals, i, slot, a.vtx, a.vary,
+                                             [&](const double* Rr, const double* t, const float* p, float* vary) {
+                                                 rc_light_dir<CAD>(Rr, t, light_of(ta.lights, view), p, vary + RC_VARY);
+                                             });
     }
-    x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1);
-    if ((threadIdx.x & 63) == 0 && x0 != INT32_MAX) {
-        int32_t* r = a.rect + (size_t)view * 4;
-        atomicMin(r + 0, x0);
-        atomicMin(r + 1, y0);
-        atomicMax(r + 2, x1);
-        atomicMax(r + 3, y1);
-    }
+    view_rect_add(a, view, b);
 }
 
 // the frame pixel that output pixel o of a crop x crop patch of box bb samples (extract_square_patch + resizeNN), and its key;
@@ -83,6 +61,8 @@ __device__ inline bool train_sample(const RenderArgs& a, int view, const int32_t
     return true;
 }
 
+// The two samples spell out their triangle lookup and shading (shade_of with the training stride): through one function the CAD
+// form of this kernel compiles to other registers and another occupancy, which nobody has measured.
 template <bool CAD>
 __global__ void __launch_bounds__(RENDER_BLOCK) render_train_crop(RenderArgs a, TrainArgs ta, const int32_t* bbs, const int32_t* visible,
                                                                   double pad_factor, int crop, uint8_t* train_x, uint8_t* mask_x,

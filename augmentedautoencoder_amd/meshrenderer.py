@@ -231,6 +231,7 @@ class Renderer(object):
         self._set = None
         self._ws = None
         self.lib = None
+        self._torch = None
 
     # ---- device state, created at first use ---------------------------------------
     def _open(self):
@@ -240,6 +241,7 @@ class Renderer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('the mesh rasteriser needs the GPU (libaae_hip.so): there is no CPU fallback')
         self.lib = _lib.load()
+        self._torch = torch                                      # for the per-call helpers: an import statement each would cost a call microseconds
         if self._device is None:
             self._device = torch.device('cuda', torch.cuda.current_device())
         meshes = []
@@ -260,9 +262,9 @@ class Renderer(object):
             _lib.check(self.lib, rc, 'aae_mesh_set_create')
             self._set = mesh_set
 
-    def _workspace(self, mesh, n, W, H, need=None):
+    def _workspace(self, need):
         import torch
-        need = int(self.lib.aae_render_workspace_bytes(mesh, n, W, H)) if need is None else int(need)
+        need = int(need)
         if self._ws is None or self._ws.numel() - (-self._ws.data_ptr()) % 256 < need:
             self._ws = None
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self._device)
@@ -275,8 +277,34 @@ class Renderer(object):
         return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, cols)), device=self._device)
 
     def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        return ctypes.c_void_p(self._torch.cuda.current_stream(self._device).cuda_stream)
+
+    # ---- the parts every render call has ----------------------------------------------
+    def _begin(self, W, H, *sizes):
+        """the device state is open; the frame size and the call's further sizes as ints"""
+        self._open()
+        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
+        return [int(v) for v in (W, H) + sizes]
+
+    def _out(self, shape, dtype):
+        return self._torch.empty(shape, dtype=dtype, device=self._device)
+
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def _pick_workspace(self, workspace, need):
+        """the caller's (pointer, bytes), or the renderer's own buffer of need bytes: the two workspace arguments of a call"""
+        ptr, nbytes = workspace if workspace is not None else self._workspace(need)
+        return ctypes.c_void_p(ptr), nbytes
+
+    def _call(self, name, args, timed=False):
+        """lib.<name>(*args) on the renderer's device and stream, or its _timed twin: the milliseconds of the six launches, else None"""
+        ms = (ctypes.c_float * 6)() if timed else None
+        name, args = (name + '_timed', args + (self._stream(), ms)) if timed else (name, args + (self._stream(),))
+        with self._torch.cuda.device(self._device):
+            _lib.check(self.lib, getattr(self.lib, name)(*args), name)
+        return list(ms) if timed else None
 
     # ---- rendering ------------------------------------------------------------------
     def render_batch(self, obj_id, W, H, K, Rs, ts, near, far, random_light=False, phong=None, workspace=None, return_tri=False, light=None):
@@ -285,9 +313,7 @@ class Renderer(object):
         per pixel (int32 [n,H,W], -1 = background).  One light for the batch, as one render call has: draw_light's, or the
         explicit light = (position, ambient, diffuse, specular)."""
         import torch
-        self._open()
-        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
-        W, H = int(W), int(H)
+        W, H = self._begin(W, H)
         mesh = self._meshes[obj_id]
         Rd = self._upload(Rs, 9)
         n = Rd.shape[0]
@@ -297,18 +323,12 @@ class Renderer(object):
             raise ValueError('%d rotations, %d translations' % (n, td.shape[0]))
         light, a, d, s = draw_light(random_light, phong, self.model) if light is None else light
         p = render_params(W, H, K, t_arr if td is None else None, near, far, 1.0, light, a, d, s)
-        with torch.cuda.device(self._device):
-            bgr = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self._device)
-            depth = torch.empty((n, H, W), dtype=torch.float32, device=self._device)
-            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
-            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
-            tri = torch.empty((n, H, W), dtype=torch.int32, device=self._device) if return_tri else None
-            ws_ptr, ws_bytes = workspace if workspace is not None else self._workspace(mesh, n, W, H)
-            rc = self.lib.aae_render_frames(mesh, ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(td.data_ptr()) if td is not None else None, n,
-                                            ctypes.byref(p), ctypes.c_void_p(bgr.data_ptr()), ctypes.c_void_p(depth.data_ptr()),
-                                            ctypes.c_void_p(tri.data_ptr()) if return_tri else None, ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes,
-                                            self._stream())
-        _lib.check(self.lib, rc, 'aae_render_frames')
+        bgr, depth = self._out((n, H, W, 3), torch.uint8), self._out((n, H, W), torch.float32)
+        bbs, vis = self._out((n, 4), torch.int32), self._out((n,), torch.int32)
+        tri = self._out((n, H, W), torch.int32) if return_tri else None
+        ptr = self._ptr
+        self._call('aae_render_frames', (mesh, ptr(Rd), ptr(td), n, ctypes.byref(p), ptr(bgr), ptr(depth), ptr(tri), ptr(bbs), ptr(vis))
+                   + self._pick_workspace(workspace, self.lib.aae_render_workspace_bytes(mesh, n, W, H)))
         if return_tri:
             return bgr, depth, bbs, vis, tri
         return bgr, depth, bbs, vis
@@ -319,27 +339,17 @@ class Renderer(object):
         translation: (crops uint8 [n,crop,crop,3] BGR, obj_bbs int32 [n,4], visible int32 [n]) as device tensors; with
         timed=True also the milliseconds of the six launches."""
         import torch
-        self._open()
-        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
-        W, H, crop = int(W), int(H), int(crop)
+        W, H, crop = self._begin(W, H, crop)
         mesh = self._meshes[obj_id]
         Rd = self._upload(Rs, 9)
         n = Rd.shape[0]
         light, a, d, s = draw_light(random_light, phong, self.model)
         p = render_params(W, H, K, t, near, far, pad_factor, light, a, d, s)
-        with torch.cuda.device(self._device):
-            crops = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
-            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
-            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
-            ws_ptr, ws_bytes = workspace if workspace is not None else self._workspace(mesh, n, W, H)
-            args = (mesh, ctypes.c_void_p(Rd.data_ptr()), n, ctypes.byref(p), crop, ctypes.c_void_p(crops.data_ptr()), ctypes.c_void_p(bbs.data_ptr()),
-                    ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
-            if timed:
-                ms = (ctypes.c_float * 6)()
-                _lib.check(self.lib, self.lib.aae_render_embedding_views_timed(*(args + (ms,))), 'aae_render_embedding_views_timed')
-                return crops, bbs, vis, list(ms)
-            _lib.check(self.lib, self.lib.aae_render_embedding_views(*args), 'aae_render_embedding_views')
-        return crops, bbs, vis
+        crops, bbs, vis = self._out((n, crop, crop, 3), torch.uint8), self._out((n, 4), torch.int32), self._out((n,), torch.int32)
+        ptr = self._ptr
+        ms = self._call('aae_render_embedding_views', (mesh, ptr(Rd), n, ctypes.byref(p), crop, ptr(crops), ptr(bbs), ptr(vis))
+                        + self._pick_workspace(workspace, self.lib.aae_render_workspace_bytes(mesh, n, W, H)), timed)
+        return (crops, bbs, vis, ms) if timed else (crops, bbs, vis)
 
     def render_training_views(self, obj_id, W, H, K, Rs, t, near, far, pad_factor, crop, lights, offsets, phong=None, workspace=None, timed=False):
         """n passes of the loop of dataset.py:238-303 at one translation, the geometry of a pair rendered once: lights [n,6]
@@ -349,9 +359,7 @@ class Renderer(object):
         train_y has the default light with phong's constants.  A view that covers no pixel has flag 0, zero crops and a mask
         of all ones."""
         import torch
-        self._open()
-        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
-        W, H, crop = int(W), int(H), int(crop)
+        W, H, crop = self._begin(W, H, crop)
         mesh = self._meshes[obj_id]
         Rd = self._upload(Rs, 9)
         n = Rd.shape[0]
@@ -361,25 +369,14 @@ class Renderer(object):
             raise ValueError('%d rotations, %d lights, %d offsets' % (n, Ld.shape[0], Od.shape[0]))
         light, a, d, s = draw_light(False, phong, self.model)
         p = render_params(W, H, K, t, near, far, pad_factor, light, a, d, s)
-        with torch.cuda.device(self._device):
-            train_x = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
-            train_y = torch.empty((n, crop, crop, 3), dtype=torch.uint8, device=self._device)
-            mask_x = torch.empty((n, crop, crop), dtype=torch.uint8, device=self._device)
-            bbs = torch.empty((n, 4), dtype=torch.int32, device=self._device)
-            vis = torch.empty((n,), dtype=torch.int32, device=self._device)
-            if workspace is not None:
-                ws_ptr, ws_bytes = workspace
-            else:
-                ws_ptr, ws_bytes = self._workspace(mesh, n, W, H, need=self.lib.aae_render_training_workspace_bytes(mesh, n, W, H))
-            args = (mesh, ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(Ld.data_ptr()), ctypes.c_void_p(Od.data_ptr()), n, ctypes.byref(p), crop,
-                    ctypes.c_void_p(train_x.data_ptr()), ctypes.c_void_p(mask_x.data_ptr()), ctypes.c_void_p(train_y.data_ptr()),
-                    ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()), ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
-            if timed:
-                ms = (ctypes.c_float * 6)()
-                _lib.check(self.lib, self.lib.aae_render_training_views_timed(*(args + (ms,))), 'aae_render_training_views_timed')
-                return train_x, mask_x.view(torch.bool), train_y, bbs, vis, list(ms)
-            _lib.check(self.lib, self.lib.aae_render_training_views(*args), 'aae_render_training_views')
-        return train_x, mask_x.view(torch.bool), train_y, bbs, vis
+        train_x, train_y = self._out((n, crop, crop, 3), torch.uint8), self._out((n, crop, crop, 3), torch.uint8)
+        mask_x, bbs, vis = self._out((n, crop, crop), torch.uint8), self._out((n, 4), torch.int32), self._out((n,), torch.int32)
+        ptr = self._ptr
+        ms = self._call('aae_render_training_views', (mesh, ptr(Rd), ptr(Ld), ptr(Od), n, ctypes.byref(p), crop, ptr(train_x), ptr(mask_x), ptr(train_y),
+                                                      ptr(bbs), ptr(vis))
+                        + self._pick_workspace(workspace, self.lib.aae_render_training_workspace_bytes(mesh, n, W, H)), timed)
+        out = (train_x, mask_x.view(torch.bool), train_y, bbs, vis)
+        return out + (ms,) if timed else out
 
     def render(self, obj_id, W, H, K, R, t, near, far, random_light=False, phong=None):
         """meshrenderer_phong.py:101-168 / meshrenderer.py:84-137: (bgr uint8 [H,W,3], depth float32 [H,W]) on the host."""
@@ -396,9 +393,7 @@ class Renderer(object):
         equal depth the earlier draw.  obj_bbs[d] is the box of draw d rendered alone (render_many's), visible[d] = 0 when it
         covers no pixel.  One light for the call.  At most 256 draws a call: split by scene."""
         import torch
-        self._open()
-        assert W <= Renderer.MAX_FBO_WIDTH and H <= Renderer.MAX_FBO_HEIGHT
-        W, H, S = int(W), int(H), int(n_scenes)
+        W, H, S = self._begin(W, H, n_scenes)
         obj = np.ascontiguousarray(np.asarray(obj_ids, dtype=np.int32).reshape(-1))
         scn = np.ascontiguousarray(np.asarray(scene_ids, dtype=np.int32).reshape(-1))
         D = len(obj)
@@ -413,29 +408,15 @@ class Renderer(object):
             raise ValueError('aae_render_scenes: %d draws, %d rotations, %d translations' % (D, Rd.shape[0], td.shape[0]))
         light, a, d, s = draw_light(random_light, phong, self.model)
         p = render_params(W, H, K, None, near, far, 1.0, light, a, d, s)
-        with torch.cuda.device(self._device):
-            bgr = torch.empty((S, H, W, 3), dtype=torch.uint8, device=self._device)
-            depth = torch.empty((S, H, W), dtype=torch.float32, device=self._device)
-            bbs = torch.empty((D, 4), dtype=torch.int32, device=self._device)
-            vis = torch.empty((D,), dtype=torch.int32, device=self._device)
-            draw = torch.empty((S, H, W), dtype=torch.int32, device=self._device) if return_ids else None
-            tri = torch.empty((S, H, W), dtype=torch.int32, device=self._device) if return_ids else None
-            if workspace is not None:
-                ws_ptr, ws_bytes = workspace
-            else:
-                ws_ptr, ws_bytes = self._workspace(None, D, W, H, need=self.lib.aae_render_scenes_workspace_bytes(self._set, D, S, W, H))
-            args = (self._set, obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                    ctypes.c_void_p(Rd.data_ptr()), ctypes.c_void_p(td.data_ptr()), D, S, ctypes.byref(p), ctypes.c_void_p(bgr.data_ptr()),
-                    ctypes.c_void_p(depth.data_ptr()), ctypes.c_void_p(draw.data_ptr()) if return_ids else None,
-                    ctypes.c_void_p(tri.data_ptr()) if return_ids else None, ctypes.c_void_p(bbs.data_ptr()), ctypes.c_void_p(vis.data_ptr()),
-                    ctypes.c_void_p(ws_ptr), ws_bytes, self._stream())
-            if timed:
-                ms = (ctypes.c_float * 6)()
-                _lib.check(self.lib, self.lib.aae_render_scenes_timed(*(args + (ms,))), 'aae_render_scenes_timed')
-            else:
-                _lib.check(self.lib, self.lib.aae_render_scenes(*args), 'aae_render_scenes')
+        bgr, depth = self._out((S, H, W, 3), torch.uint8), self._out((S, H, W), torch.float32)
+        bbs, vis = self._out((D, 4), torch.int32), self._out((D,), torch.int32)
+        draw, tri = (self._out((S, H, W), torch.int32), self._out((S, H, W), torch.int32)) if return_ids else (None, None)
+        ptr = self._ptr
+        ms = self._call('aae_render_scenes', (self._set, obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              ptr(Rd), ptr(td), D, S, ctypes.byref(p), ptr(bgr), ptr(depth), ptr(draw), ptr(tri), ptr(bbs), ptr(vis))
+                        + self._pick_workspace(workspace, self.lib.aae_render_scenes_workspace_bytes(self._set, D, S, W, H)), timed)
         out = (bgr, depth, bbs, vis) + ((draw, tri) if return_ids else ())
-        return out + (list(ms),) if timed else out
+        return out + (ms,) if timed else out
 
     def render_many(self, obj_ids, W, H, K, Rs, ts, near, far, random_light=None, phong=None):
         """meshrenderer.py:140-194 / meshrenderer_phong.py:170-224: the models obj_ids at the poses (Rs[i], ts[i]) in one frame with

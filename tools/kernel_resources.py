@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Compile the library with -Rpass-analysis=kernel-resource-usage and print one line per kernel:
-VGPRs / AGPRs / SGPR + VGPR spills / scratch / occupancy / LDS.  Usage: python tools/kernel_resources.py [regex] [-o out.so] [--reuse]"""
+VGPRs / AGPRs / SGPR + VGPR spills / scratch / occupancy / LDS.  Usage: python tools/kernel_resources.py [regex] [-o out.so] [--reuse]
+[--unit aae_hip]   (--unit names the translation unit under csrc/: aae_hip, aae_wino, aae_render, aae_icp)"""
 import os
 import re
 import subprocess
@@ -9,9 +10,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith('-') else None
 out = sys.argv[sys.argv.index('-o') + 1] if '-o' in sys.argv else '/tmp/aae_resources_build.so'
+unit = sys.argv[sys.argv.index('--unit') + 1] if '--unit' in sys.argv else 'aae_hip'
 cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
-       os.path.join(ROOT, 'augmentedautoencoder_amd', 'csrc', 'aae_hip.hip'), '-o', out, '-Rpass-analysis=kernel-resource-usage']
-log = '/tmp/aae_resources.log'
+       os.path.join(ROOT, 'augmentedautoencoder_amd', 'csrc', unit + '.hip'), '-o', out, '-Rpass-analysis=kernel-resource-usage']
+log = '/tmp/aae_resources.log' if unit == 'aae_hip' else '/tmp/aae_resources_%s.log' % unit
 if '--reuse' in sys.argv and os.path.exists(log):          # summarise the remarks of the previous build again
     err = open(log).read()
 else:
@@ -33,7 +35,7 @@ for line in err.splitlines():
         cur[k.strip()] = v.strip()
 names = subprocess.run(['c++filt'], input='\n'.join(r['name'] for r in rows).encode(), stdout=subprocess.PIPE).stdout.decode().splitlines()
 for r, n in zip(rows, names):
-    n = n.replace('void ', '').replace('aae::', '')
+    n = n.replace('void ', '').replace('aae_render::', '').replace('aae::', '')
     n = n[:n.find('(')] if '(' in n else n
     if pat and not pat.search(n):
         continue
