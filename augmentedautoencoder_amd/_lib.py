@@ -22,6 +22,9 @@ AAE_MODEL_RECONST, AAE_MODEL_CAD = 0, 1
 AAE_SCENE_MAX_DRAWS = 256
 AAE_ICP_MAX_PROBLEMS, AAE_ICP_MAX_POINTS = 16, 4096
 AAE_ICP_DEPTH_ONLY, AAE_ICP_NO_DEPTH, AAE_ICP_NO_DEPTH_ZERO_T = 1, 2, 4
+AAE_AUGMENT_MAX_OPS, AAE_AUGMENT_MAX_BLUR_K = 16, 15
+AAE_AUGMENT_AFFINE, AAE_AUGMENT_DROPOUT, AAE_AUGMENT_BLUR, AAE_AUGMENT_ADD = 1, 2, 3, 4
+AAE_AUGMENT_INVERT, AAE_AUGMENT_MULTIPLY, AAE_AUGMENT_CONTRAST = 5, 6, 7
 
 LIB_NAME = 'libaae_hip.so'
 # the same sources with -DAAE_EXPERIMENTS: every kernel variant that measured slower than the defaults + the profiling / ablation
@@ -52,6 +55,7 @@ EXPORTED_SYMBOLS = (
     'aae_mesh_set_create', 'aae_mesh_set_destroy', 'aae_render_scenes_workspace_bytes', 'aae_render_scenes', 'aae_render_scenes_timed',
     'aae_overlay_blend',
     'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
+    'aae_augment_max_image_bytes', 'aae_augment_batch',
 )
 
 
@@ -90,6 +94,16 @@ class RenderParams(Structure):
 class IcpShape(Structure):
     """aae_icp_shape"""
     _fields_ = [('n_problems', c_int32), ('max_points', c_int32), ('W', c_int32), ('H', c_int32), ('crop_w', c_int32), ('crop_h', c_int32)]
+
+
+class AugmentOp(Structure):
+    """aae_augment_op"""
+    _fields_ = [('code', c_int32), ('i', c_int32 * 4), ('f', c_float * 3)]
+
+
+class AugmentShape(Structure):
+    """aae_augment_shape"""
+    _fields_ = [('N', c_int32), ('M', c_int32), ('H', c_int32), ('W', c_int32), ('C', c_int32), ('B', c_int32), ('aux_words', c_int32)]
 
 
 class MultiItem(Structure):
@@ -269,6 +283,15 @@ def declare_icp(lib):
     return lib
 
 
+def declare_augment(lib):
+    """The training-batch kernel's entry points (aae_augment.hip: like the rasteriser, part of the GPU library only)."""
+    lib.aae_augment_max_image_bytes.restype = c_size_t
+    lib.aae_augment_max_image_bytes.argtypes = []
+    lib.aae_augment_batch.restype = c_int
+    lib.aae_augment_batch.argtypes = [POINTER(AugmentShape)] + [c_void_p] * 13
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -289,7 +312,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare_icp(declare_render(declare(ctypes.CDLL(path))))
+    lib = declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path)))))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -6,11 +6,16 @@ looks for first).
 ``render_embedding_image_batch`` delegates to a pluggable *view source*; ``MeshViewSource`` is the one that renders the
 object's mesh on the GPU (meshrenderer.py, the HIP rasteriser) in place of the reference's OpenGL context.  The training
 pairs come from the same rasteriser (``Renderer.render_training_views``): the images are this rasteriser's, not an OpenGL
-driver's, and parity with a driver is unpinned exactly as for the codebook views.  ``Dataset.batch``, the background images
-and the augmentation pipeline stay out of scope (imgaug and cv2 are not dependencies).
+driver's, and parity with a driver is unpinned exactly as for the codebook views.
+
+``load_bg_images``, ``batch`` and ``batch_device`` are the training loop's side (dataset.py:146-174, 456-495): the background
+composite, the ``[Augmentation] CODE`` chain and the /255 run as one HIP launch per batch (augmentation.py; imgaug and cv2 are
+not dependencies).  The two occlusion switches and every augmenter outside the template's seven are refused by name.
 """
 from __future__ import annotations
 
+import ast
+import glob
 import hashlib
 import os
 
@@ -210,6 +215,104 @@ class Dataset(object):
             self.train_x[a:e] = x.cpu().numpy()
             self.mask_x[a:e] = m.cpu().numpy()
             self.train_y[a:e] = y.cpu().numpy()
+
+    # ---- the training batches (dataset.py:24-25, 146-174, 456-495) ----------------------------------------------------------
+    @lazy_property
+    def bg_img_paths(self):
+        return glob.glob(self._kw['background_images_glob'])
+
+    @lazy_property
+    def noof_bg_imgs(self):
+        return min(int(self._kw['noof_bg_imgs']), len(self.bg_img_paths))
+
+    @lazy_property
+    def _aug_plan(self):
+        from . import augmentation
+        return augmentation.parse_code(self._kw['code'])
+
+    def _refuse_occlusion(self):
+        """REALISTIC_OCCLUSION / SQUARE_OCCLUSION (dataset.py:470-474): rejection loops over mask data this package has no file
+        format for; the template has both off"""
+        for key in ('realistic_occlusion', 'square_occlusion'):
+            if ast.literal_eval(str(self._kw.get(key, 'False')).strip()):
+                raise NotImplementedError('[Augmentation] %s: %s is not implemented; set it to False' % (key.upper(), self._kw[key]))
+
+    def load_bg_images(self, dataset_path):
+        """dataset.py:146-174: bg_imgs uint8 [noof_bg_imgs,H,W,C] from <md5(str(shape) + str(noof_bg_imgs) + str(glob))>.npy in
+        dataset_path, or cut from the first noof_bg_imgs files of the glob at random anchors (random.shuffle of the list, then
+        np.random.rand() for y and for x per file, the reference's order) and saved there.  Deviations: the array starts as zeros
+        (the reference leaves np.empty garbage for a file it skips as too small), and files are decoded by PIL's codecs into BGR,
+        not by cv2.imread (JPEG decoders may differ in the last grey level).  PIL is imported only when files are decoded."""
+        name = hashlib.md5((str(self.shape) + str(self.noof_bg_imgs) + str(self._kw['background_images_glob'])).encode('utf-8')).hexdigest()
+        current_file_name = os.path.join(dataset_path, name + '.npy')
+        if os.path.exists(current_file_name):
+            self.bg_imgs = np.load(current_file_name)
+        else:
+            from random import shuffle
+            from PIL import Image
+            h, w, c = self.shape
+            if c != 3:
+                raise NotImplementedError('C = %d: the grey-scale conversion (cv2.cvtColor, dataset.py:167-168) is not implemented; use C = 3' % c)
+            self.bg_imgs = np.zeros((self.noof_bg_imgs,) + self.shape, dtype=np.uint8)
+            file_list = self.bg_img_paths[:self.noof_bg_imgs]
+            shuffle(file_list)
+            for j, fname in enumerate(file_list):
+                with Image.open(fname) as im:
+                    bgr = np.asarray(im.convert('RGB'))[:, :, ::-1]
+                H, W = bgr.shape[:2]
+                y_anchor = int(np.random.rand() * (H - h))
+                x_anchor = int(np.random.rand() * (W - w))
+                bgr = bgr[y_anchor:y_anchor + h, x_anchor:x_anchor + w, :]
+                if bgr.shape[0] != h or bgr.shape[1] != w:
+                    continue
+                self.bg_imgs[j] = bgr
+            np.save(current_file_name, self.bg_imgs)
+        print('loaded %s bg images' % self.noof_bg_imgs)
+        return current_file_name
+
+    def to_device(self, device='cuda'):
+        """train_x, mask_x, train_y and bg_imgs uploaded once; batch_device and batch read them from there"""
+        import torch
+        from . import augmentation
+        augmentation.check_image_bytes(self.shape)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt, copy=False)).to(device)
+        if np.shape(self.train_x)[1:] != np.shape(self.bg_imgs)[1:]:
+            raise ValueError('training images of %s, backgrounds of %s' % (np.shape(self.train_x)[1:], np.shape(self.bg_imgs)[1:]))
+        self._device_arrays = (up(self.train_x, np.uint8), up(self.mask_x, bool), up(self.train_y, np.uint8), up(self.bg_imgs, np.uint8))
+        return self
+
+    def _draw_batch(self, batch_size):
+        """np.random in the reference's order: the two choice(..., replace=False) calls of dataset.py:461-465, then -- on the first
+        batch only -- whatever np.random.rand() the CODE text holds (the reference's lazy ``_aug`` is first touched at
+        dataset.py:488, after the choices), then draw_programs"""
+        from . import augmentation
+        self._refuse_occlusion()
+        n_train, n_bg = len(self.train_x), len(self.bg_imgs)            # the reference's noof_training_imgs and noof_bg_imgs
+        rand_idcs = np.random.choice(n_train, batch_size, replace=False)
+        assert n_bg > 0
+        rand_idcs_bg = np.random.choice(n_bg, batch_size, replace=False)
+        plan = self._aug_plan
+        return rand_idcs, rand_idcs_bg, augmentation.draw_programs(plan, batch_size, self.train_x.shape[1:])
+
+    def _on_device(self):
+        if not hasattr(self, '_device_arrays'):
+            self.to_device()
+        return self._device_arrays
+
+    def batch_device(self, batch_size):
+        """dataset.py:456-495 as one launch: (batch_x, batch_y) float32 device tensors [batch_size,H,W,C] in [0,1]"""
+        from . import augmentation
+        rand_idcs, rand_idcs_bg, programs = self._draw_batch(batch_size)
+        _, x, y = augmentation.run_batch(*self._on_device(), rand_idcs, rand_idcs_bg, programs, want_u8=False)
+        return x, y
+
+    def batch(self, batch_size):
+        """dataset.py:456-495: (batch_x, batch_y) as the reference returns them, NumPy float64 ``uint8 / 255.``, batch_x from the
+        kernel's uint8 output"""
+        from . import augmentation
+        rand_idcs, rand_idcs_bg, programs = self._draw_batch(batch_size)
+        x, _, _ = augmentation.run_batch(*self._on_device(), rand_idcs, rand_idcs_bg, programs, want_x=False, want_y=False)
+        return x.cpu().numpy() / 255., np.asarray(self.train_y)[rand_idcs] / 255.
 
     def extract_square_patch(self, scene_img, bb_xywh, pad_factor, resize=(128, 128), interpolation='nearest', black_borders=False):
         """dataset.py:354-373 on the host in NumPy, with cv2.resize(INTER_NEAREST) restated (OpenCV resize.cpp, resizeNN);

@@ -506,6 +506,51 @@ int aae_icp_refine_timed(const aae_icp_shape* shape, const int32_t* n_points, co
                          double* mean_error_out, int32_t* error_out, double* d2_out, int32_t* idx_out, void* workspace,
                          size_t ws_bytes, void* stream, float* kernel_ms);
 
+/* ---- training batches: Dataset.batch (auto_pose/ae/dataset.py:456-495) in one launch --------------------------------
+ * One workgroup per batch image: x = mask ? bg : train_x is composited into LDS, the image's op program runs there
+ * (uint8 between ops; every real result is clipped to [0,255] and rounded half to even), and the result is written as
+ * uint8 and / or as float32(v / 255.).  csrc/kernels/augment_core.h states the arithmetic of every op; DESIGN section 4
+ * lists the imgaug 0.4.0 semantics it assumes.  Random numbers are drawn by the caller: a program holds only values. */
+#define AAE_AUGMENT_MAX_OPS 16
+#define AAE_AUGMENT_MAX_BLUR_K 15
+#define AAE_AUGMENT_AFFINE 1    /* f[0] = 1 / scale                                                                      */
+#define AAE_AUGMENT_DROPOUT 2   /* i[0] mask bits, i[1] row table, i[2] column table (word offsets into aux); i[3] =
+                                   h_s * w_s when per channel, else 0.  row table: int32 [H] cell row * w_s; column table:
+                                   int32 [W] cell column; bit (c * i[3] + row + column) set = dropped                     */
+#define AAE_AUGMENT_BLUR 3      /* i[0] = k (odd, <= AAE_AUGMENT_MAX_BLUR_K, k / 2 < min(H, W)), i[1] = word offset of
+                                   k normalised float32 weights in aux                                                   */
+#define AAE_AUGMENT_ADD 4       /* f[c] = integer added to channel c                                                     */
+#define AAE_AUGMENT_INVERT 5    /* i[c] != 0: 255 - x on channel c                                                       */
+#define AAE_AUGMENT_MULTIPLY 6  /* f[c] = factor of channel c                                                            */
+#define AAE_AUGMENT_CONTRAST 7  /* f[c] = alpha of channel c: 128 + alpha * (x - 128)                                    */
+
+typedef struct aae_augment_op {
+    int32_t code;
+    int32_t i[4];
+    float f[3];
+} aae_augment_op;
+
+typedef struct aae_augment_shape {
+    int32_t N, M;                 /* training images, background images                                           */
+    int32_t H, W, C;              /* C <= 3; H * W * C <= aae_augment_max_image_bytes()                           */
+    int32_t B;                    /* batch size = workgroups                                                      */
+    int32_t aux_words;            /* dwords in aux                                                                */
+} aae_augment_shape;
+
+/* the largest H * W * C: two image buffers must fit the workgroup's LDS (81920; 128 x 128 x 3 is 49152) */
+size_t aae_augment_max_image_bytes(void);
+
+/* All pointers device-resident.  train_x / train_y uint8 [N,H,W,C], mask_x one byte per pixel [N,H,W] (non-zero =
+ * background), bg uint8 [M,H,W,C]; train_idx / bg_idx / n_ops int32 [B]; ops [B, AAE_AUGMENT_MAX_OPS]; aux uint32
+ * [aux_words] (NULL when 0).  Outputs [B,H,W,C], each may be NULL: batch_x_u8, batch_x_f32 = float32(x / 255.),
+ * batch_y_f32 = float32(train_y / 255.).  An image over the LDS limit is refused with AAE_ERR_UNSUPPORTED naming the
+ * limit, and nothing is launched.  The kernel trusts no index: an image whose train_idx / bg_idx is out of range is
+ * left unwritten, an op whose aux ranges do not lie inside aux is skipped.  One launch on `stream`, no allocation, no
+ * synchronisation. */
+int aae_augment_batch(const aae_augment_shape* shape, const void* train_x, const void* mask_x, const void* train_y, const void* bg,
+                      const int32_t* train_idx, const int32_t* bg_idx, const int32_t* n_ops, const aae_augment_op* ops,
+                      const uint32_t* aux, void* batch_x_u8, float* batch_x_f32, float* batch_y_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
