@@ -25,6 +25,8 @@ AAE_ICP_DEPTH_ONLY, AAE_ICP_NO_DEPTH, AAE_ICP_NO_DEPTH_ZERO_T = 1, 2, 4
 AAE_AUGMENT_MAX_OPS, AAE_AUGMENT_MAX_BLUR_K = 16, 15
 AAE_AUGMENT_AFFINE, AAE_AUGMENT_DROPOUT, AAE_AUGMENT_BLUR, AAE_AUGMENT_ADD = 1, 2, 3, 4
 AAE_AUGMENT_INVERT, AAE_AUGMENT_MULTIPLY, AAE_AUGMENT_CONTRAST = 5, 6, 7
+AAE_LOSS_L2, AAE_LOSS_L1 = 0, 1
+AAE_LOSS_MAX_BATCH, AAE_LOSS_MAX_N, AAE_LOSS_MAX_LATENT = 65536, 4194304, 1048576
 
 LIB_NAME = 'libaae_hip.so'
 # the same sources with -DAAE_EXPERIMENTS: every kernel variant that measured slower than the defaults + the profiling / ablation
@@ -56,6 +58,7 @@ EXPORTED_SYMBOLS = (
     'aae_overlay_blend',
     'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
     'aae_augment_max_image_bytes', 'aae_augment_batch',
+    'aae_recon_loss_workspace_bytes', 'aae_recon_loss', 'aae_latent_reg_loss',
 )
 
 
@@ -104,6 +107,11 @@ class AugmentOp(Structure):
 class AugmentShape(Structure):
     """aae_augment_shape"""
     _fields_ = [('N', c_int32), ('M', c_int32), ('H', c_int32), ('W', c_int32), ('C', c_int32), ('B', c_int32), ('aux_words', c_int32)]
+
+
+class ReconLossDesc(Structure):
+    """aae_recon_loss_desc"""
+    _fields_ = [('B', c_int32), ('n', c_int32), ('kind', c_int32), ('bootstrap_ratio', c_int32)]
 
 
 class MultiItem(Structure):
@@ -292,6 +300,17 @@ def declare_augment(lib):
     return lib
 
 
+def declare_loss(lib):
+    """The loss kernels' entry points (aae_loss.hip: like the rasteriser, part of the GPU library only)."""
+    lib.aae_recon_loss_workspace_bytes.restype = c_size_t
+    lib.aae_recon_loss_workspace_bytes.argtypes = [c_int, c_int]
+    lib.aae_recon_loss.restype = c_int
+    lib.aae_recon_loss.argtypes = [POINTER(ReconLossDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.aae_latent_reg_loss.restype = c_int
+    lib.aae_latent_reg_loss.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -312,7 +331,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path)))))
+    lib = declare_loss(declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path))))))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -4,8 +4,8 @@ encoder, decoder, codebook, ``build_codebook_from_name`` and ``restore_checkpoin
 
 The cfg keys are parsed once, by ``EncoderConfig.from_cfg`` / ``DecoderConfig.from_cfg``
 (weights.py); the builders below only hand the parsed shapes to the API classes.  Builders of
-the training graph (queue, autoencoder loss, train op) raise ``NotImplementedError``: training
-is outside the scope of this package.  Configuration errors raise instead of ``exit()``-ing.
+the training graph (queue, train op) raise ``NotImplementedError``; ``build_ae`` gives the
+autoencoder's loss as a fetchable, without a backward pass.  Configuration errors raise instead of ``exit()``-ing.
 """
 from __future__ import annotations
 
@@ -14,6 +14,7 @@ import os
 
 from . import session as S
 from . import utils as u
+from .ae import AE
 from .codebook import Codebook
 from .dataset import Dataset
 from .decoder import Decoder
@@ -62,8 +63,12 @@ def _training_only(name):
     return refuse
 
 
+def build_ae(encoder, decoder, args):
+    """ae_factory.py:73-77."""
+    return AE(encoder, decoder, args.getfloat('Network', 'NORM_REGULARIZE'), args.getfloat('Network', 'VARIATIONAL'))
+
+
 build_queue = _training_only('build_queue')
-build_ae = _training_only('build_ae')
 build_train_op = _training_only('build_train_op')
 
 

@@ -5,7 +5,9 @@
 Reference call sites kept working (auto_pose/eval/eval_plots.py:24-34,37-72,75-80):
     sess.run(decoder.x, feed_dict={encoder.x: crops})            # encode, then reconstruct
     sess.run(decoder.x, feed_dict={decoder._latent_code: codes}) # reconstruct given codes
-The training-only members (reconstr_loss, bootstrap loss, mask loss) are out of scope."""
+and the number the training loop logs (auto_pose/ae/ae_train.py):
+    sess.run(decoder.reconstr_loss, feed_dict={encoder.x: batch_x, decoder.reconstruction_target: batch_y})
+The mask head (auxiliary_mask) and its loss are not provided."""
 from __future__ import annotations
 
 import numpy as np
@@ -29,6 +31,8 @@ class Decoder(object):
         self._num_filters = list(num_filters)
         self._kernel_size = int(kernel_size)
         self._strides = list(strides)
+        from .loss import loss_kind
+        loss_kind(loss)                          # an unknown name is refused here (the reference prints and calls exit())
         self._loss = loss
         self._bootstrap_ratio = bootstrap_ratio
         self._batch_normalization = bool(batch_norm)
@@ -44,6 +48,7 @@ class Decoder(object):
         self._engine = None
         self._device = None
         self._x_op = S.Op('decoder/x', self._run)
+        self._loss_op = S.Op('decoder/reconstr_loss', lambda feed: self.reconstr_loss_device(feed)[0].cpu().numpy()[0])
         S.register(decoder=self)
 
     @property
@@ -54,6 +59,33 @@ class Decoder(object):
     def x(self):
         """Fetchable reconstruction [B,H,W,C] float32 in [0,1] (decoder.py:36-84)."""
         return self._x_op
+
+    @property
+    def reconstr_loss(self):
+        """Fetchable float32 scalar (decoder.py:86-132): the decoder's `loss` ('L2' / 'L1') between the reconstruction and
+        decoder.reconstruction_target, over the n // bootstrap_ratio largest errors of each image when bootstrap_ratio > 1.
+        Feed encoder.x (or decoder._latent_code) and decoder.reconstruction_target."""
+        if self._auxiliary_mask:
+            raise NotImplementedError('auxiliary_mask=True adds the mask head (_xmask) and its mask loss to reconstr_loss; the decoder '
+                                      'engine does not compute the mask head')
+        return self._loss_op
+
+    def reconstr_loss_device(self, feed, grad=False):
+        """(loss [1], per_image [B], dx or None, reconstruction [B,H,W,C]) as device tensors: encode (or take the fed latent
+        codes), decode and evaluate the loss without leaving the device."""
+        from .loss import reconstruction_loss
+        if self._auxiliary_mask:
+            self.reconstr_loss
+        target = None
+        for k, v in feed.items():
+            if k is self._reconstruction_target:
+                target = v
+        if target is None:
+            raise ValueError('feed_dict has no value for decoder.reconstruction_target')
+        x = self._reconstruct(feed)
+        target = self.engine.target_batch(target, tuple(x.shape))
+        loss, per_image, dx = reconstruction_loss(x, target, loss=self._loss, bootstrap_ratio=self._bootstrap_ratio, grad=grad)
+        return loss, per_image, dx, x
 
     # -- plumbing ------------------------------------------------------------------
     def load_weights(self, weights, device=None):
@@ -81,11 +113,15 @@ class Decoder(object):
             self._engine = DecoderEngine(self.config, self.weights, device=self._device)
         return self._engine
 
-    def _run(self, feed):
+    def _reconstruct(self, feed):
+        """Decoder.x as a device tensor"""
         for k, v in feed.items():
             if k is self._latent_code:
-                return self.engine.decode(np.asarray(v, dtype=np.float32)).cpu().numpy()
+                return self.engine.decode(v if hasattr(v, 'is_cuda') else np.asarray(v, dtype=np.float32))
         if self._encoder is None:
             raise ValueError('feed_dict has no value for decoder._latent_code')
         z = self._encoder.engine.encode_checked(self._encoder._feed(feed))  # stays on the device
-        return self.engine.decode(z).cpu().numpy()
+        return self.engine.decode(z)
+
+    def _run(self, feed):
+        return self._reconstruct(feed).cpu().numpy()

@@ -54,6 +54,18 @@ class Encoder(object):
             return a.reshape(a.shape[0], -1).cpu().numpy()
         return S.Op('encoder/encoder_out', run)
 
+    @property
+    def reg_loss(self):
+        """Fetchable float32 scalar (encoder.py:97-100): mean_b | ||z_b|| - 1 |."""
+        return S.Op('encoder/reg_loss', lambda feed: self.reg_loss_device(feed)[0].cpu().numpy()[0])
+
+    def reg_loss_device(self, feed, grad=False, z=None):
+        """(loss [1], dz or None) as device tensors; z: the latent codes when the caller has encoded already"""
+        from .loss import latent_reg_loss
+        if z is None:
+            z = self.engine.encode_checked(self._feed(feed))
+        return latent_reg_loss(z, grad=grad)
+
     # -- plumbing --------------------------------------------------------------
     def _feed(self, feed):
         for k, v in feed.items():

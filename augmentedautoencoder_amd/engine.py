@@ -877,6 +877,18 @@ class DecoderEngine(object):
             return [(self.lib.aae_decoder_kernel_label(self.handle, i).decode(), float(ms[i]),
                      float(self.lib.aae_decoder_kernel_flops(self.handle, i))) for i in range(n.value)]
 
+    def target_batch(self, target, shape):
+        """a reconstruction target (np.ndarray or torch.Tensor, float) as a contiguous float32 device tensor of `shape`"""
+        torch = _torch()
+        if isinstance(target, np.ndarray):
+            target = torch.from_numpy(np.ascontiguousarray(target, dtype=np.float32))
+        elif not torch.is_tensor(target):
+            raise TypeError('the reconstruction target must be a numpy array or a torch tensor, got %r' % type(target))
+        t = target.to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('the reconstruction target has shape %s, the reconstruction %s' % (tuple(t.shape), tuple(shape)))
+        return t
+
     def decode(self, z, out=None):
         """Decoder.x: device float32 [B,H,W,C] in [0,1].  out: the caller's tensor to decode into (contiguous float32
         [B,H,W,C] on the engine's device; returned) -- every element of it is written."""

@@ -551,6 +551,37 @@ int aae_augment_batch(const aae_augment_shape* shape, const void* train_x, const
                       const int32_t* train_idx, const int32_t* bg_idx, const int32_t* n_ops, const aae_augment_op* ops,
                       const uint32_t* aux, void* batch_x_u8, float* batch_x_f32, float* batch_y_f32, void* stream);
 
+/* ---- The training loss: bootstrapped L2 / L1 reconstruction loss and the latent-norm regulariser (the reference's
+ * auto_pose/ae/decoder.py:86-132, encoder.py:97-100), with their gradients with respect to the tensors they read. ------- */
+#define AAE_LOSS_L2 0
+#define AAE_LOSS_L1 1
+#define AAE_LOSS_MAX_BATCH 65536      /* B of both calls                                                              */
+#define AAE_LOSS_MAX_N 4194304        /* n = H * W * C of one image                                                   */
+#define AAE_LOSS_MAX_LATENT 1048576   /* J                                                                            */
+
+typedef struct aae_recon_loss_desc { int32_t B, n, kind /* 0 = L2, 1 = L1 */, bootstrap_ratio; } aae_recon_loss_desc;
+
+/* bytes of workspace aae_recon_loss needs (16-byte aligned); 0 for a B or n outside the limits */
+size_t aae_recon_loss_workspace_bytes(int B, int n);
+
+/* x / target device float32 [B, n].  e = (x - t)^2 (L2) or |x - t| (L1) in fp32.  bootstrap_ratio > 1: per image the
+ * k = n / bootstrap_ratio (integer division) largest errors are selected, among equal errors the lowest indices first
+ * (tf.nn.top_k); bootstrap_ratio = 1: every element.  per_image[b] = mean of image b's selected errors, loss = mean of
+ * per_image over B.  dx[b, i] = 2 (x - t) / (B k) (L2) or sign(x - t) / (B k) (L1) on a selected element, 0 elsewhere;
+ * every element of dx is written.  per_image and dx may be NULL.  A NaN error ranks above every number: that image's
+ * mean and the loss are NaN, the other images are unaffected, the call returns AAE_OK.  Refused with nothing launched:
+ * a NULL desc / x / target / loss / workspace (AAE_ERR_INVALID), B < 1, n < 1, bootstrap_ratio < 1, a kind other than
+ * the two, k = 0 (AAE_ERR_INVALID), B or n over the limits above (AAE_ERR_UNSUPPORTED), a short or misaligned workspace
+ * (AAE_ERR_WORKSPACE).  Two launches on `stream`; no allocation, no synchronisation, no host copy, no floating-point
+ * atomic (the same inputs give the same bits); capturable. */
+int aae_recon_loss(const aae_recon_loss_desc* d, const float* x, const float* target,
+                   float* loss /* [1] */, float* per_image /* [B] or null */, float* dx /* [B*n] or null */,
+                   void* workspace, size_t ws_bytes, void* stream);
+
+/* z device float32 [B, J].  loss = mean_b | ||z_b|| - 1 |;  dz[b] = sign(||z_b|| - 1) z_b / ||z_b|| / B, 0 for a zero
+ * row (dz may be NULL).  One launch on `stream`, no workspace, no allocation, no synchronisation; capturable. */
+int aae_latent_reg_loss(const float* z, int B, int J, float* loss /* [1] */, float* dz /* [B*J] or null */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
