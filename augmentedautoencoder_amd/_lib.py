@@ -59,6 +59,9 @@ EXPORTED_SYMBOLS = (
     'aae_icp_workspace_bytes', 'aae_icp_workspace_info', 'aae_icp_prepare', 'aae_icp_refine', 'aae_icp_refine_timed',
     'aae_augment_max_image_bytes', 'aae_augment_batch',
     'aae_recon_loss_workspace_bytes', 'aae_recon_loss', 'aae_latent_reg_loss',
+    'aae_upconv_backward_workspace_bytes', 'aae_upconv_backward', 'aae_dense_backward_workspace_bytes', 'aae_dense_backward',
+    'aae_decoder_get_desc', 'aae_decoder_backward_workspace_bytes', 'aae_decoder_backward', 'aae_decoder_backward_timed',
+    'aae_decoder_bwd_label_count', 'aae_decoder_bwd_label',
 )
 
 
@@ -112,6 +115,17 @@ class AugmentShape(Structure):
 class ReconLossDesc(Structure):
     """aae_recon_loss_desc"""
     _fields_ = [('B', c_int32), ('n', c_int32), ('kind', c_int32), ('bootstrap_ratio', c_int32)]
+
+
+class UpconvBackwardDesc(Structure):
+    """aae_upconv_backward_desc"""
+    _fields_ = [('B', c_int32), ('H', c_int32), ('W', c_int32), ('Cin', c_int32), ('UH', c_int32), ('UW', c_int32), ('Cout', c_int32), ('KS', c_int32),
+                ('act', c_int32)]
+
+
+class DenseBackwardDesc(Structure):
+    """aae_dense_backward_desc"""
+    _fields_ = [('B', c_int32), ('J', c_int32), ('U', c_int32)]
 
 
 class MultiItem(Structure):
@@ -311,6 +325,32 @@ def declare_loss(lib):
     return lib
 
 
+def declare_decoder_bwd(lib):
+    """The decoder's backward pass (aae_decoder_bwd.hip: part of the GPU library only)."""
+    lib.aae_upconv_backward_workspace_bytes.restype = c_size_t
+    lib.aae_upconv_backward_workspace_bytes.argtypes = [POINTER(UpconvBackwardDesc), c_int]
+    lib.aae_upconv_backward.restype = c_int
+    lib.aae_upconv_backward.argtypes = [POINTER(UpconvBackwardDesc)] + [c_void_p] * 8 + [c_size_t, c_void_p]
+    lib.aae_dense_backward_workspace_bytes.restype = c_size_t
+    lib.aae_dense_backward_workspace_bytes.argtypes = [POINTER(DenseBackwardDesc), c_int]
+    lib.aae_dense_backward.restype = c_int
+    lib.aae_dense_backward.argtypes = [POINTER(DenseBackwardDesc)] + [c_void_p] * 8 + [c_size_t, c_void_p]
+    lib.aae_decoder_get_desc.restype = c_int
+    lib.aae_decoder_get_desc.argtypes = [c_void_p, POINTER(DecoderDesc)]
+    lib.aae_decoder_backward_workspace_bytes.restype = c_size_t
+    lib.aae_decoder_backward_workspace_bytes.argtypes = [c_void_p, c_int]
+    chain = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.aae_decoder_backward.restype = c_int
+    lib.aae_decoder_backward.argtypes = chain
+    lib.aae_decoder_backward_timed.restype = c_int
+    lib.aae_decoder_backward_timed.argtypes = chain + [POINTER(c_float), c_int, POINTER(c_int)]
+    lib.aae_decoder_bwd_label_count.restype = c_int
+    lib.aae_decoder_bwd_label_count.argtypes = []
+    lib.aae_decoder_bwd_label.restype = c_char_p
+    lib.aae_decoder_bwd_label.argtypes = [c_int]
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -331,7 +371,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare_loss(declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path))))))
+    lib = declare_decoder_bwd(declare_loss(declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path)))))))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -1,5 +1,6 @@
 """``AE`` with the constructor and properties of the reference's auto_pose/ae/ae.py:11-53: the encoder and decoder of one
-autoencoder and the loss its training minimises, as a fetchable evaluated on the device.  There is no backward pass behind it."""
+autoencoder and the loss its training minimises, as a fetchable evaluated on the device; gradients_device() adds the decoder's
+backward pass (the encoder's and the optimiser are not built)."""
 from __future__ import annotations
 
 import numpy as np
@@ -63,6 +64,26 @@ class AE(object):
             reg = enc.reg_loss_device(feed, z=z)[0]
             loss = loss + reg * torch.tensor(np.float32(self._norm_regularize), dtype=torch.float32, device=loss.device)
         return loss
+
+    def gradients_device(self, feed):
+        """(loss [1], OrderedDict decoder variable -> gradient, dz) as device tensors: the loss of AE.loss, the gradient of every
+        decoder variable, and dL/dz with float32(norm_regularize) * d(reg_loss)/dz added in -- what an encoder backward starts from."""
+        import torch
+        dec, enc = self._decoder, self._encoder
+        z = next((v for k, v in feed.items() if k is dec._latent_code), None)
+        if z is None:
+            z = enc.engine.encode_checked(enc._feed(feed))
+        z = dec.engine._z(z)
+        feed = dict(feed)
+        feed[dec._latent_code] = z
+        loss, grads, dz = dec.gradients_device(feed)
+        if self._norm_regularize > 0:
+            from .loss import latent_reg_loss
+            reg, dz_reg = latent_reg_loss(z, grad=True)
+            scale = torch.tensor(np.float32(self._norm_regularize), dtype=torch.float32, device=loss.device)
+            loss = loss + reg * scale
+            dz = dz + dz_reg * scale
+        return loss, grads, dz
 
     def _loss(self, feed):
         return self.loss_device(feed).cpu().numpy()[0]

@@ -379,6 +379,12 @@ double aae_decoder_kernel_flops(const aae_decoder* dec, int i) {
     return dec->ctx.records[i].flops;
 }
 
+int aae_decoder_get_desc(const aae_decoder* dec, aae_decoder_desc* out) {
+    if (!dec || !out) return aae_host::fail(AAE_ERR_INVALID, "aae_decoder_get_desc: null argument");
+    *out = dec->desc;
+    return AAE_OK;
+}
+
 int aae_decoder_activation_info(const aae_decoder* dec, int B, int stage, size_t* offset_bytes, size_t* count) {
     using namespace aae_host;
     if (!dec || !offset_bytes || !count || B < 1) return fail(AAE_ERR_INVALID, "aae_decoder_activation_info: bad argument");

@@ -87,6 +87,25 @@ class Decoder(object):
         loss, per_image, dx = reconstruction_loss(x, target, loss=self._loss, bootstrap_ratio=self._bootstrap_ratio, grad=grad)
         return loss, per_image, dx, x
 
+    def gradients_device(self, feed):
+        """(loss [1], OrderedDict variable name -> gradient, dz) as device tensors: decode, the loss with its gradient, the decoder's
+        backward pass.  Nothing is updated: there is no optimiser behind this."""
+        from .decoder_grad import check_trainable
+        check_trainable(self.config)
+        z = None
+        for k, v in feed.items():
+            if k is self._latent_code:
+                z = self.engine._z(v if hasattr(v, 'is_cuda') else np.asarray(v, dtype=np.float32))
+        if z is None:
+            if self._encoder is None:
+                raise ValueError('feed_dict has no value for decoder._latent_code')
+            z = self.engine._z(self._encoder.engine.encode_checked(self._encoder._feed(feed)))
+        feed = dict(feed)
+        feed[self._latent_code] = z
+        loss, _, dx, x = self.reconstr_loss_device(feed, grad=True)
+        grads, dz = self.engine.backward(z, x, dx)
+        return loss, grads, dz
+
     # -- plumbing ------------------------------------------------------------------
     def load_weights(self, weights, device=None):
         """Stand-in for Saver.restore on the decoder variables (dense_1, conv2d_<L>.., BN)."""

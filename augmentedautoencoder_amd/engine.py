@@ -834,11 +834,18 @@ class DecoderEngine(object):
         self.handle = handle
         self.ws = _Workspace(self.device)
         self._last_B = None
+        self._host_weights = arrays             # what backward() differentiates with respect to: copied to the device on first use
+        dense, convs, final, _ = cfg.variable_names(weights)
+        self._grad_names = [n + s for n in [dense] + list(convs) + [final] for s in ('/kernel', '/bias')]
+        self._dev_weights = None
+        self._bwd_ws = None
 
     def close(self):
         if getattr(self, 'handle', None):
             self.lib.aae_decoder_destroy(self.handle)
             self.handle = None
+        self._dev_weights = None
+        self._bwd_ws = None
 
     def __del__(self):
         try:
@@ -921,6 +928,70 @@ class DecoderEngine(object):
             raise ValueError('decode_timed takes at most max_batch=%d codes' % self.max_batch)
         out = torch.empty((z.shape[0],) + tuple(self.cfg.shape), dtype=torch.float32, device=self.device)
         return out, self._chunk(z, out, timed=True)
+
+    def gradient_names(self):
+        """the decoder's variables in the order of aae_decoder_create: kernel and bias of the dense layer, of every hidden
+        convolution, of the output convolution"""
+        return list(self._grad_names)
+
+    def check_trainable(self):
+        """NotImplementedError for what the backward pass is not built for"""
+        from .decoder_grad import check_trainable
+        check_trainable(self.cfg)
+
+    def device_weights(self):
+        """device copies of the weights the engine was created from, in checkpoint shapes (made on first use)"""
+        torch = _torch()
+        if self._dev_weights is None:
+            self._dev_weights = [torch.from_numpy(np.array(a)).to(self.device) for a in self._host_weights]
+        return self._dev_weights
+
+    def backward(self, z, x, dx, out=None, timed=False):
+        """The gradient of every decoder variable and dL/dz from dx = dL/dx, after decode(z) -> x of the same batch (one chunk:
+        the hidden activations are read from the engine's workspace).  Returns (OrderedDict name -> tensor in checkpoint shape, dz
+        [B, latent]); out: an OrderedDict of the caller's tensors to write into.  timed=True: also the list of
+        (label, milliseconds) per launch (synchronises)."""
+        import collections
+        torch = _torch()
+        self.check_trainable()
+        z = self._z(z)
+        B = int(z.shape[0])
+        if self._last_B is None or B != self._last_B or B > self.max_batch:
+            raise ValueError('backward() takes the batch of the last decode() as a single chunk: that was %s codes (max_batch %d), this is %d'
+                             % (self._last_B, self.max_batch, B))
+        shape = (B,) + tuple(self.cfg.shape)
+        for t, name in ((x, 'x'), (dx, 'dx')):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError('%s must be a contiguous float32 device tensor of shape %s' % (name, shape))
+        weights = self.device_weights()
+        names = self.gradient_names()
+        if out is None:
+            grads = collections.OrderedDict((n, torch.empty_like(w)) for n, w in zip(names, weights))
+        else:
+            grads = collections.OrderedDict((n, out[n]) for n in names)
+            for (n, g), w in zip(grads.items(), weights):
+                if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or not g.is_contiguous() or g.shape != w.shape:
+                    raise ValueError('out[%r] must be a contiguous float32 tensor of shape %s on %s' % (n, tuple(w.shape), w.device))
+        dz = torch.empty_like(z)
+        need = int(self.lib.aae_decoder_backward_workspace_bytes(self.handle, B))
+        if need == 0:
+            _lib.check(self.lib, -2, 'aae_decoder_backward_workspace_bytes')
+        if self._bwd_ws is None or self._bwd_ws.numel() < need:
+            self._bwd_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _, fwd_ptr = self.ws.get(0)
+        n = len(weights)
+        wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
+        gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads.values()])
+        args = [self.handle, B, ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(dx.data_ptr()), ctypes.c_void_p(fwd_ptr), wp, gp,
+                ctypes.c_void_p(dz.data_ptr()), ctypes.c_void_p(self._bwd_ws.data_ptr()), int(self._bwd_ws.numel()), _stream_ptr(torch)]
+        with _on_device(self.device):
+            if not timed:
+                _lib.check(self.lib, self.lib.aae_decoder_backward(*args), 'aae_decoder_backward')
+                return grads, dz
+            ms = (ctypes.c_float * 64)()
+            cnt = ctypes.c_int(0)
+            _lib.check(self.lib, self.lib.aae_decoder_backward_timed(*(args + [ms, 64, ctypes.byref(cnt)])), 'aae_decoder_backward_timed')
+        return grads, dz, [(self.lib.aae_decoder_bwd_label(i).decode(), float(ms[i])) for i in range(cnt.value)]
 
     def activation(self, stage):
         """Hidden activation of the most recent single-chunk decode: stage 0 = dense output

@@ -582,6 +582,48 @@ int aae_recon_loss(const aae_recon_loss_desc* d, const float* x, const float* ta
  * row (dz may be NULL).  One launch on `stream`, no workspace, no allocation, no synchronisation; capturable. */
 int aae_latent_reg_loss(const float* z, int B, int J, float* loss /* [1] */, float* dz /* [B*J] or null */, void* stream);
 
+/* ---- The decoder's backward pass: the gradient of every variable of a stage and dL/d(input), from dL/d(output) and the
+ * activations the forward left behind.  A stage is: nearest resize of a_in [B,H,W,Cin] to UH x UW
+ * (iy = min(y H / UH, H - 1)), KS x KS 'same' stride-1 convolution with w [KS,KS,Cin,Cout], bias, activation -> a_out.
+ *   delta = g_out where a_out > 0 else 0 (ReLU, act 0);  (g_out a_out)(1 - a_out) in that order, fp32 (sigmoid, act 1)
+ *   db[co] = sum delta;  dw[kh,kw,ci,co] = sum up(a_in)[b,y+kh-p,x+kw-p,ci] delta[b,y,x,co];  g_in = the transposed convolution
+ * Exact 2x stages run phase-folded (four U x U problems on the source grid, U = (KS + 1) / 2), 1x stages as the one-phase case;
+ * any other resize is refused with AAE_ERR_UNSUPPORTED and nothing launched (the forward's direct kernel runs it; training it is
+ * not built).  No floating-point atomic: the same inputs give the same bits.  No allocation, synchronisation or host copy;
+ * capturable.  Every tensor is a 16-byte aligned device float32 array; g_in / dz may be NULL (that product is not computed). */
+typedef struct aae_upconv_backward_desc { int32_t B, H, W, Cin, UH, UW, Cout, KS, act /* 0 = ReLU, 1 = sigmoid */; } aae_upconv_backward_desc;
+typedef struct aae_dense_backward_desc { int32_t B, J, U; } aae_dense_backward_desc;
+
+/* bytes of workspace (256-byte aligned) the call needs; 0 for a shape the call refuses */
+size_t aae_upconv_backward_workspace_bytes(const aae_upconv_backward_desc* d, int with_g_in);
+int aae_upconv_backward(const aae_upconv_backward_desc* d, const float* a_in, const float* a_out, const float* g_out,
+                        const float* w_hwio, float* dw /* [KS,KS,Cin,Cout] */, float* db /* [Cout] */,
+                        float* g_in /* [B,H,W,Cin] or null */, void* workspace, size_t ws_bytes, void* stream);
+
+/* the dense layer a_out = relu(z w + b), z [B,J], w [J,U]:  dw = z^T delta, db = sum_b delta, dz = delta w^T */
+size_t aae_dense_backward_workspace_bytes(const aae_dense_backward_desc* d, int with_dz);
+int aae_dense_backward(const aae_dense_backward_desc* d, const float* z, const float* a_out, const float* g_out,
+                       const float* w, float* dw /* [J,U] */, float* db /* [U] */, float* dz /* [B,J] or null */,
+                       void* workspace, size_t ws_bytes, void* stream);
+
+/* The whole decoder, after aae_decoder_forward(dec, z, B, x, forward_workspace, ...) of the same batch: dx = dL/dx [B,H,W,C] in,
+ * the gradient of every variable out.  weights[] / grads[]: device pointers in the order of aae_decoder_create (kernel, bias per
+ * layer, dense first), in checkpoint shapes; the weights are the caller's current ones (the folded copies are made on the device per
+ * call).  dz [B, latent] may be NULL.  forward_workspace is only read.  Refused with AAE_ERR_UNSUPPORTED and nothing launched: a
+ * decoder with batch_norm (training-mode statistics are not built), a stage whose resize is neither exactly 2x nor 1x.
+ * The timed twin synchronises the stream and returns the time between launches (labels: aae_decoder_bwd_label). */
+int aae_decoder_get_desc(const aae_decoder* dec, aae_decoder_desc* out);
+size_t aae_decoder_backward_workspace_bytes(const aae_decoder* dec, int B);
+int aae_decoder_backward(const aae_decoder* dec, int B, const float* z, const float* x, const float* dx, const void* forward_workspace,
+                         const float* const* weights, float* const* grads, float* dz, void* workspace, size_t ws_bytes, void* stream);
+int aae_decoder_backward_timed(const aae_decoder* dec, int B, const float* z, const float* x, const float* dx, const void* forward_workspace,
+                               const float* const* weights, float* const* grads, float* dz, void* workspace, size_t ws_bytes, void* stream,
+                               float* kernel_ms, int max_kernels, int* n_kernels);
+
+/* what the last backward call of the calling thread launched, in launch order: "<stage>:<form> M= N= K= ... splits=" */
+int aae_decoder_bwd_label_count(void);
+const char* aae_decoder_bwd_label(int i);
+
 #ifdef __cplusplus
 }
 #endif
