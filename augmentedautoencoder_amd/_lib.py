@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = (
     'aae_upconv_backward_workspace_bytes', 'aae_upconv_backward', 'aae_dense_backward_workspace_bytes', 'aae_dense_backward',
     'aae_decoder_get_desc', 'aae_decoder_backward_workspace_bytes', 'aae_decoder_backward', 'aae_decoder_backward_timed',
     'aae_decoder_bwd_label_count', 'aae_decoder_bwd_label',
+    'aae_conv_backward_workspace_bytes', 'aae_conv_backward', 'aae_linear_backward_workspace_bytes', 'aae_linear_backward',
+    'aae_encoder_get_desc', 'aae_encoder_backward_workspace_bytes', 'aae_encoder_backward', 'aae_encoder_backward_timed',
+    'aae_encoder_bwd_label_count', 'aae_encoder_bwd_label',
 )
 
 
@@ -126,6 +129,11 @@ class UpconvBackwardDesc(Structure):
 class DenseBackwardDesc(Structure):
     """aae_dense_backward_desc"""
     _fields_ = [('B', c_int32), ('J', c_int32), ('U', c_int32)]
+
+
+class ConvBackwardDesc(Structure):
+    """aae_conv_backward_desc"""
+    _fields_ = [('B', c_int32), ('H', c_int32), ('W', c_int32), ('Cin', c_int32), ('Cout', c_int32), ('KS', c_int32), ('S', c_int32), ('x_dtype', c_int32)]
 
 
 class MultiItem(Structure):
@@ -351,6 +359,32 @@ def declare_decoder_bwd(lib):
     return lib
 
 
+def declare_encoder_bwd(lib):
+    """The encoder's backward pass (aae_encoder_bwd.hip: part of the GPU library only)."""
+    lib.aae_conv_backward_workspace_bytes.restype = c_size_t
+    lib.aae_conv_backward_workspace_bytes.argtypes = [POINTER(ConvBackwardDesc)]
+    lib.aae_conv_backward.restype = c_int
+    lib.aae_conv_backward.argtypes = [POINTER(ConvBackwardDesc)] + [c_void_p] * 8 + [c_size_t, c_void_p]
+    lib.aae_linear_backward_workspace_bytes.restype = c_size_t
+    lib.aae_linear_backward_workspace_bytes.argtypes = [POINTER(DenseBackwardDesc), c_int]
+    lib.aae_linear_backward.restype = c_int
+    lib.aae_linear_backward.argtypes = [POINTER(DenseBackwardDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]
+    lib.aae_encoder_get_desc.restype = c_int
+    lib.aae_encoder_get_desc.argtypes = [c_void_p, POINTER(EncoderDesc)]
+    lib.aae_encoder_backward_workspace_bytes.restype = c_size_t
+    lib.aae_encoder_backward_workspace_bytes.argtypes = [c_void_p, c_int]
+    chain = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.aae_encoder_backward.restype = c_int
+    lib.aae_encoder_backward.argtypes = chain
+    lib.aae_encoder_backward_timed.restype = c_int
+    lib.aae_encoder_backward_timed.argtypes = chain + [POINTER(c_float), c_int, POINTER(c_int)]
+    lib.aae_encoder_bwd_label_count.restype = c_int
+    lib.aae_encoder_bwd_label_count.argtypes = []
+    lib.aae_encoder_bwd_label.restype = c_char_p
+    lib.aae_encoder_bwd_label.argtypes = [c_int]
+    return lib
+
+
 def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), EXPERIMENTS_LIB_NAME if experiments_requested() else LIB_NAME)
 
@@ -371,7 +405,7 @@ def load():
         raise RuntimeError(
             '%s not built: run `python -c "import __graft_entry__ as g; g.build(%s)"` at the repo root '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.' % (path, 'experiments=True' if experiments_requested() else ''))
-    lib = declare_decoder_bwd(declare_loss(declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path)))))))
+    lib = declare_encoder_bwd(declare_decoder_bwd(declare_loss(declare_augment(declare_icp(declare_render(declare(ctypes.CDLL(path))))))))
     if lib.aae_abi_version() != AAE_ABI_VERSION:
         raise RuntimeError('libaae_hip.so ABI version %d != expected %d' % (lib.aae_abi_version(), AAE_ABI_VERSION))
     _LIB = lib

@@ -1,6 +1,6 @@
 """``AE`` with the constructor and properties of the reference's auto_pose/ae/ae.py:11-53: the encoder and decoder of one
 autoencoder and the loss its training minimises, as a fetchable evaluated on the device; gradients_device() adds the decoder's
-backward pass (the encoder's and the optimiser are not built)."""
+backward pass, variable_gradients_device() the encoder's behind it (the optimiser is not built)."""
 from __future__ import annotations
 
 import numpy as np
@@ -84,6 +84,24 @@ class AE(object):
             loss = loss + reg * scale
             dz = dz + dz_reg * scale
         return loss, grads, dz
+
+    def variable_gradients_device(self, feed):
+        """(loss [1], OrderedDict variable -> gradient) as device tensors, over every encoder variable and then every decoder
+        variable, in checkpoint shapes: gradients_device() of a batch encoded here, then the encoder's backward pass from its dz.
+        The latent code is computed from the encoder's input: a feed that supplies decoder._latent_code has no encoder gradient."""
+        import collections
+        dec, enc = self._decoder, self._encoder
+        if any(k is dec._latent_code for k in feed):
+            raise ValueError('variable_gradients_device differentiates through the encoder: feed its input, not decoder._latent_code')
+        enc.engine.check_trainable()
+        loss, dec_grads, dz = self.gradients_device(feed)
+        enc_grads, _ = enc.gradients_device(feed, dz.contiguous())
+        grads = collections.OrderedDict(enc_grads)
+        for name, g in dec_grads.items():
+            if name in grads:
+                raise ValueError('the encoder and the decoder both have a variable named %r' % name)
+            grads[name] = g
+        return loss, grads
 
     def _loss(self, feed):
         return self.loss_device(feed).cpu().numpy()[0]

@@ -291,6 +291,12 @@ int aae_has_experiments(void) {
 
 int aae_encoder_split_precision_for_batch(const aae_encoder* enc, int B) { return (enc && B >= 1 && aae_host::runs_split(enc, B)) ? 1 : 0; }
 
+int aae_encoder_get_desc(const aae_encoder* enc, aae_encoder_desc* out) {
+    if (!enc || !out) return aae_host::fail(AAE_ERR_INVALID, "aae_encoder_get_desc: null argument");
+    *out = enc->desc;
+    return AAE_OK;
+}
+
 int aae_encoder_activation_info(const aae_encoder* enc, int B, int layer, size_t* offset_bytes, size_t* count) {
     using namespace aae_host;
     if (!enc || !offset_bytes || !count || B < 1) return fail(AAE_ERR_INVALID, "aae_encoder_activation_info: bad argument");

@@ -12,10 +12,17 @@
 // slabs are kept k-major in LDS ([32 k][128 rows], [32 k][32 NT columns]) -- a straight copy in, and a fragment read is 32
 // consecutive words.  The data gradient and the dense dz contract over channels, the fast index: they use the row-major slabs of
 // tile_f32.h (mfma_slab).  No atomics: every output element has one writer and every sum one order.
+// The kernels that are no templates are `inline`: the encoder's backward pass (encoder_bwd_f32.h, another translation unit) launches
+// delta_bias_kernel, column_sum_finish_kernel, dense_dw_kernel, dense_dz_kernel and splitk_sum_kernel too.
 #pragma once
 
 #include "decoder_bwd_core.h"
 #include "tile_f32.h"
+
+#if defined(__clang__)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"      // (an `inline` kernel: one definition per library, which is what is meant)
+#endif
 
 namespace aae_bwd {
 
@@ -53,7 +60,7 @@ struct DeltaBiasArgs {
 
 // grid (ceil(C / cw), chunks): the block's 256 / cw row lanes walk the chunk's rows, a lane's sum is one chain in row order, the
 // lanes are added in lane order
-__global__ __launch_bounds__(BWD_BLOCK) void delta_bias_kernel(DeltaBiasArgs a) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void delta_bias_kernel(DeltaBiasArgs a) {
     __shared__ float sums[BWD_BLOCK];
     const int t = threadIdx.x, cl = t & (a.cw - 1), rl = t / a.cw, nrl = BWD_BLOCK / a.cw;
     const int c = blockIdx.x * a.cw + cl;
@@ -77,7 +84,7 @@ __global__ __launch_bounds__(BWD_BLOCK) void delta_bias_kernel(DeltaBiasArgs a) 
 }
 
 // out[c] = partial[0][c] + partial[1][c] + ... in that order
-__global__ __launch_bounds__(BWD_BLOCK) void column_sum_finish_kernel(const float* partial, int chunks, int C, float* out) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void column_sum_finish_kernel(const float* partial, int chunks, int C, float* out) {
     const int c = blockIdx.x * BWD_BLOCK + threadIdx.x;
     if (c >= C) return;
     float s = partial[c];
@@ -191,7 +198,7 @@ struct WgradReduceArgs {
     int total;              // KS * KS * Cin * Cout
 };
 
-__global__ __launch_bounds__(BWD_BLOCK) void wgrad_reduce_kernel(WgradReduceArgs a) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void wgrad_reduce_kernel(WgradReduceArgs a) {
     const StageGeom g = a.g;
     for (int e = blockIdx.x * BWD_BLOCK + threadIdx.x; e < a.total; e += gridDim.x * BWD_BLOCK) {
         const int co = e % g.Cout;
@@ -218,7 +225,7 @@ struct FoldArgs {
     int total;              // P * U * U * C4 * Cin * 4
 };
 
-__global__ __launch_bounds__(BWD_BLOCK) void fold_weights_kernel(FoldArgs a) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void fold_weights_kernel(FoldArgs a) {
     const StageGeom g = a.g;
     for (int e = blockIdx.x * BWD_BLOCK + threadIdx.x; e < a.total; e += gridDim.x * BWD_BLOCK) {
         const int q = e & 3;
@@ -316,7 +323,7 @@ __global__ __launch_bounds__(BWD_BLOCK) void dgrad_kernel(DgradArgs a) {
 
 // ---- dense layer ----------------------------------------------------------------------------------------------------------------------
 // dW[j, u] = sum over b (ascending) of z[b, j] * delta[b, u]: K = B, memory-bound
-__global__ __launch_bounds__(BWD_BLOCK) void dense_dw_kernel(const float* z, const float* delta, float* dw, int B, int J, int U) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void dense_dw_kernel(const float* z, const float* delta, float* dw, int B, int J, int U) {
     const long long total = (long long)J * U;
     for (long long e = (long long)blockIdx.x * BWD_BLOCK + threadIdx.x; e < total; e += (long long)gridDim.x * BWD_BLOCK) {
         const int u = (int)(e % U), j = (int)(e / U);
@@ -389,7 +396,7 @@ __global__ __launch_bounds__(BWD_BLOCK) void dense_dz_kernel(DenseDzArgs a) {
 }
 
 // out[e] = partial[0][e] + partial[1][e] + ... in that order
-__global__ __launch_bounds__(BWD_BLOCK) void splitk_sum_kernel(const float* partial, int splits, int total, float* out) {
+inline __global__ __launch_bounds__(BWD_BLOCK) void splitk_sum_kernel(const float* partial, int splits, int total, float* out) {
     for (int e = blockIdx.x * BWD_BLOCK + threadIdx.x; e < total; e += gridDim.x * BWD_BLOCK) {
         float s = partial[e];
         for (int k = 1; k < splits; ++k) s += partial[(size_t)k * total + e];
@@ -398,3 +405,7 @@ __global__ __launch_bounds__(BWD_BLOCK) void splitk_sum_kernel(const float* part
 }
 
 }  // namespace aae_bwd
+
+#if defined(__clang__)
+#pragma clang diagnostic pop
+#endif

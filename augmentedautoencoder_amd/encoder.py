@@ -66,6 +66,14 @@ class Encoder(object):
             z = self.engine.encode_checked(self._feed(feed))
         return latent_reg_loss(z, grad=grad)
 
+    def gradients_device(self, feed, dz, need_dx=False):
+        """(OrderedDict variable name -> gradient in checkpoint shape, dx or None) as device tensors: the encoder's backward pass from
+        dz = dL/dz [B, latent], after an encode of the batch in `feed` (the engine's last forward: its activations are read from the
+        workspace).  Nothing is updated: there is no optimiser behind this."""
+        from .encoder_grad import check_trainable
+        check_trainable(self.config)
+        return self.engine.backward(self._feed(feed), dz, need_dx=need_dx)
+
     # -- plumbing --------------------------------------------------------------
     def _feed(self, feed):
         for k, v in feed.items():

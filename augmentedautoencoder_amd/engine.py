@@ -170,11 +170,16 @@ class EncoderEngine(object):
         self.x3h_fallback = True
         self.x3h_fallbacks = 0             # how many chunks were recomputed
         self._x3h_pending = []             # (flag slot, redo closure) of f32x3h forwards not yet checked
+        self._host_weights = arrays        # what backward() differentiates with respect to: copied to the device on first use
+        self._dev_weights = None
+        self._bwd_ws = None
 
     def close(self):
         if getattr(self, 'handle', None):
             self.lib.aae_encoder_destroy(self.handle)
             self.handle = None
+        self._dev_weights = None
+        self._bwd_ws = None
 
     def __del__(self):
         try:
@@ -437,6 +442,75 @@ class EncoderEngine(object):
             return ((pairs[:, 0, :] + pairs[:, 1, :]).reshape(self._last_B, Ho, Wo, Co)
                     / 2.0 ** self.options.get('x3h_act_shift', 4)).to(torch.float32)
         return raw.view(torch.float32).reshape(self._last_B, Ho, Wo, Co).clone()
+
+    # ---- the backward pass --------------------------
+    def gradient_names(self):
+        """the encoder's variables in the order of aae_encoder_create: kernel and bias of every convolution, then of the dense layer"""
+        from .weights import conv_names
+        return [n + s for n in list(conv_names(self.cfg.num_layers)) + ['dense'] for s in ('/kernel', '/bias')]
+
+    def check_trainable(self):
+        """NotImplementedError for what the backward pass is not built for"""
+        from .encoder_grad import check_trainable
+        check_trainable(self.cfg)
+
+    def device_weights(self):
+        """device copies of the weights the engine was created from, in checkpoint shapes (made on first use)"""
+        torch = _torch()
+        if self._dev_weights is None:
+            self._dev_weights = [torch.from_numpy(np.array(a)).to(self.device) for a in self._host_weights]
+        return self._dev_weights
+
+    def backward(self, x, dz, out=None, need_dx=False, timed=False):
+        """The gradient of every encoder variable from dz = dL/dz [B, latent], after encode(x) of the same batch (one chunk: the
+        layer activations are read from the engine's workspace).  Returns (OrderedDict name -> tensor in checkpoint shape, dx
+        [B,H,W,C] float32 or None); out: an OrderedDict of the caller's tensors to write into.  timed=True: also the list of
+        (label, milliseconds) per launch (synchronises).  NotImplementedError, with nothing launched: batch norm, a stride of 3 or
+        more, a forward that ran in split precision or with compact_workspace."""
+        import collections
+        torch = _torch()
+        self.check_trainable()
+        t = self.to_device_batch(x)
+        B = int(t.shape[0])
+        if self._last_B is None or B != self._last_B or B > self.max_batch:
+            raise ValueError('backward() takes the batch of the last encode() as a single chunk: that was %s crops (max_batch %d), this is %d'
+                             % (self._last_B, self.max_batch, B))
+        if not isinstance(dz, torch.Tensor) or dz.dtype != torch.float32 or not dz.is_cuda or not dz.is_contiguous() or tuple(dz.shape) != (B, self.cfg.latent_space_size):
+            raise ValueError('dz must be a contiguous float32 device tensor of shape %s' % ((B, self.cfg.latent_space_size),))
+        weights = self.device_weights()
+        names = self.gradient_names()
+        if out is None:
+            grads = collections.OrderedDict((n, torch.empty_like(w)) for n, w in zip(names, weights))
+        else:
+            grads = collections.OrderedDict((n, out[n]) for n in names)
+            for (n, g), w in zip(grads.items(), weights):
+                if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or not g.is_contiguous() or g.shape != w.shape:
+                    raise ValueError('out[%r] must be a contiguous float32 tensor of shape %s on %s' % (n, tuple(w.shape), w.device))
+        dx = torch.empty(t.shape, dtype=torch.float32, device=self.device) if need_dx else None
+        need = max(int(self.lib.aae_encoder_backward_workspace_bytes(self.handle, B)), 256)         # (0: the call below says why it refuses)
+        if self._bwd_ws is None or self._bwd_ws.numel() < need:
+            self._bwd_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _, fwd_ptr = self.ws.get(0)
+        n = len(weights)
+        wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
+        gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads.values()])
+        dt = _lib.AAE_DTYPE_U8 if t.dtype == torch.uint8 else _lib.AAE_DTYPE_F32
+        args = [self.handle, B, ctypes.c_void_p(t.data_ptr()), dt, ctypes.c_void_p(dz.data_ptr()), ctypes.c_void_p(fwd_ptr), wp, gp,
+                ctypes.c_void_p(dx.data_ptr()) if need_dx else None, ctypes.c_void_p(self._bwd_ws.data_ptr()), int(self._bwd_ws.numel()), _stream_ptr(torch)]
+        ms = (ctypes.c_float * 64)()
+        cnt = ctypes.c_int(0)
+        with _on_device(self.device):
+            if timed:
+                rc, what = self.lib.aae_encoder_backward_timed(*(args + [ms, 64, ctypes.byref(cnt)])), 'aae_encoder_backward_timed'
+            else:
+                rc, what = self.lib.aae_encoder_backward(*args), 'aae_encoder_backward'
+        if rc == -2:
+            msg = self.lib.aae_last_error()
+            raise NotImplementedError(msg.decode('utf-8', 'replace') if msg else what)
+        _lib.check(self.lib, rc, what)
+        if not timed:
+            return grads, dx
+        return grads, dx, [(self.lib.aae_encoder_bwd_label(i).decode(), float(ms[i])) for i in range(cnt.value)]
 
 
 class CodebookEngine(object):

@@ -624,6 +624,51 @@ int aae_decoder_backward_timed(const aae_decoder* dec, int B, const float* z, co
 int aae_decoder_bwd_label_count(void);
 const char* aae_decoder_bwd_label(int i);
 
+/* ---- The encoder's backward pass: the gradient of every variable of a layer and dL/d(input), from dL/d(output) and the
+ * activations the forward left behind.  A layer is a KS x KS TF-'same' convolution of stride S with
+ * w [KS,KS,Cin,Cout] (Ho = ceil(H / S); padding before = total / 2, the odd pixel at the end), bias, ReLU -> a_out [B,Ho,Wo,Cout].
+ *   delta = g_out where a_out > 0 else 0;  db[co] = sum delta
+ *   dw[kh,kw,ci,co] = sum a_in[b, S oy + kh - pt, S ox + kw - pl, ci] delta[b,oy,ox,co]   (taps in the padding contribute nothing)
+ *   g_in[b,iy,ix,ci] = sum delta[b,oy,ox,co] w[kh,kw,ci,co] over S oy + kh - pt = iy, S ox + kw - pl = ix
+ * The data gradient runs by input parity (iy mod S, ix mod S): each class is a stride-1 problem over the taps it sees; a class
+ * without a tap (KS 1, S 2) is written with zeros.  a_in is float32, or uint8 read as float32(v / 255.) (x_dtype: AAE_DTYPE_*),
+ * the two inputs the forward's first layer takes.  Strides 1 and 2, KS 1 ... 7; a stride of 3 or more is refused with
+ * AAE_ERR_UNSUPPORTED and nothing launched.  No floating-point atomic: the same inputs give the same bits.  No allocation,
+ * synchronisation or host copy; capturable.  Every tensor is 16-byte aligned; g_in / g_a / dx may be NULL (not computed). */
+typedef struct aae_conv_backward_desc { int32_t B, H, W, Cin, Cout, KS, S, x_dtype /* of a_in: AAE_DTYPE_U8 | AAE_DTYPE_F32 */; } aae_conv_backward_desc;
+
+/* bytes of workspace (256-byte aligned) the call needs; 0 for a shape the call refuses */
+size_t aae_conv_backward_workspace_bytes(const aae_conv_backward_desc* d);
+int aae_conv_backward(const aae_conv_backward_desc* d, const void* a_in, const float* a_out, const float* g_out,
+                      const float* w_hwio, float* dw /* [KS,KS,Cin,Cout] */, float* db /* [Cout] */,
+                      float* g_in /* [B,H,W,Cin] or null */, void* workspace, size_t ws_bytes, void* stream);
+
+/* the linear dense layer z = a w + b, a [B,J], w [J,U], dz = dL/dz [B,U]:  dw = a^T dz, db = sum_b dz, g_a = dz w^T */
+size_t aae_linear_backward_workspace_bytes(const aae_dense_backward_desc* d, int with_g_a);
+int aae_linear_backward(const aae_dense_backward_desc* d, const float* a, const float* dz, const float* w,
+                        float* dw /* [J,U] */, float* db /* [U] */, float* g_a /* [B,J] or null */,
+                        void* workspace, size_t ws_bytes, void* stream);
+
+/* The whole encoder, after aae_encoder_forward(enc, x, x_dtype, B, z, forward_workspace, ...) of the same batch: dz = dL/dz
+ * [B, latent] in, the gradient of every variable out.  weights[] / grads[]: device pointers in the order of aae_encoder_create
+ * (kernel, bias per conv layer, then the dense layer), in checkpoint shapes; the weights are the caller's current ones.
+ * dx [B,H,W,C] float32 may be NULL.  forward_workspace is only read: the ReLU masks and the layer inputs are the fp32 activations
+ * the forward left there.  Refused with AAE_ERR_UNSUPPORTED and nothing launched: an encoder with batch_norm (training-mode
+ * statistics are not built), a batch whose forward ran in split precision (aae_encoder_split_precision_for_batch) or with
+ * "compact_workspace" (the activations are then fp16 pairs, or overwritten), a stride of 3 or more.
+ * The timed twin synchronises the stream and returns the time between launches (labels: aae_encoder_bwd_label). */
+int aae_encoder_get_desc(const aae_encoder* enc, aae_encoder_desc* out);
+size_t aae_encoder_backward_workspace_bytes(const aae_encoder* enc, int B);
+int aae_encoder_backward(const aae_encoder* enc, int B, const void* x, int x_dtype, const float* dz, const void* forward_workspace,
+                         const float* const* weights, float* const* grads, float* dx, void* workspace, size_t ws_bytes, void* stream);
+int aae_encoder_backward_timed(const aae_encoder* enc, int B, const void* x, int x_dtype, const float* dz, const void* forward_workspace,
+                               const float* const* weights, float* const* grads, float* dx, void* workspace, size_t ws_bytes, void* stream,
+                               float* kernel_ms, int max_kernels, int* n_kernels);
+
+/* what the last encoder-backward call of the calling thread launched, in launch order: "<layer>:<form> M= N= K= ... splits=" */
+int aae_encoder_bwd_label_count(void);
+const char* aae_encoder_bwd_label(int i);
+
 #ifdef __cplusplus
 }
 #endif

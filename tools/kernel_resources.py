@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Compile the library with -Rpass-analysis=kernel-resource-usage and print one line per kernel:
 VGPRs / AGPRs / SGPR + VGPR spills / scratch / occupancy / LDS.  Usage: python tools/kernel_resources.py [regex] [-o out.so] [--reuse]
-[--unit aae_hip]   (--unit names the translation unit under csrc/: aae_hip, aae_wino, aae_render, aae_icp, aae_augment, aae_loss, aae_decoder_bwd)"""
+[--unit aae_hip]   (--unit names the translation unit under csrc/: aae_hip, aae_wino, aae_render, aae_icp, aae_augment, aae_loss, aae_decoder_bwd, aae_encoder_bwd)"""
 import os
 import re
 import subprocess
